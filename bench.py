@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the similarity-navigated aggregation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, preheats and warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, the byte-model roofline of the whole step).  --full adds
+everything else the line below describes: the kernel-level roofline legs and floors, the
+variants, the backward and epoch figures, the CPU baseline and its check of the output, the
+cold-start figure, and at N > 1 the exchange-form check and the locality_0.8 leg.
+--dump-outputs DIR writes the last timed step's output to DIR/out.npy (float32; N > 1:
+out_rank<r>.npy per rank; above its share of 60 MB a fixed, seeded sample of whole rows, with
+their ids in out_rows.npy / out_rank<r>_rows.npy as float64).
 
 A step = one fused forward of the aggregation (F.normalize + per-edge cosine +
 top-k/threshold selection + similarity-weighted mean: SURVEY.md 8a rows a3-a8) over
@@ -44,6 +53,8 @@ The line's keys (beyond the driver's contract):
                   reference-style loop.
   --workload products also prints the ++ layer's forward+backward, its backward roofline and the
   Adam step over the dense 460 MB w (train.py:376).
+All of these but roofline.frac / achieved / algorithmic_bytes, roofline_step and roofline_layer
+are --full only.
 
 Prints ONE JSON line on rank 0.
 """
@@ -200,6 +211,25 @@ def copy_floor(table, batches=6, reps=20):
     return float(np.median(ms[1:]))
 
 
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out, path, rank, world, seed):
+    """--dump-outputs: the last timed step's output, float32, one file per rank.  An output larger than the
+    rank's share of DUMP_BUDGET_BYTES is written as a fixed sample of whole rows (seeded by --seed, sorted),
+    their ids beside it as float64."""
+    os.makedirs(path, exist_ok=True)
+    name = "out" if world == 1 else f"out_rank{rank}"
+    out = out.detach().float()
+    budget = DUMP_BUDGET_BYTES // world
+    if out.numel() * 4 > budget:
+        rows_kept = budget // (out[0].numel() * 4 + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(out.size(0), size=rows_kept, replace=False))
+        np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        out = out.index_select(0, torch.from_numpy(rows).to(out.device))
+    np.save(os.path.join(path, f"{name}.npy"), out.cpu().numpy())
+
+
 def time_loop(fn, warmup, steps, sync):
     for _ in range(warmup):
         fn()
@@ -242,7 +272,15 @@ def main():
     ap.add_argument("--no-finalize-ab", action="store_true",
                     help="skip the leg that times the same step with the split rows' finalize as a launch of its own "
                          "(profiling runs: one form of the main kernel per trace)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: kernel roofline and floors, variants, backward, epochs, CPU "
+                         "baseline and oracle check, cold start; N > 1: exchange-form check and the locality 0.8 leg "
+                         "(the --no-* options above switch legs of a --full run off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/*.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # (before anything initialises the HIP runtime, which reads it once: the host driver only
     # supports dmabuf IPC, and RCCL fails with hipIpcGetMemHandle otherwise)
@@ -369,11 +407,13 @@ def main():
         time_loop(R["step"], 0, preheat_steps, sync_all)
     dt, e_all, halo_all, out = measure(R, args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world, args.seed)
 
     # N > 1: the two exchange forms must agree on this rank's rows (RCCL all_to_all_single vs
     # all_gather_into_tensor: a self-check of the collectives on the real node)
     exchange_check = None
-    if world > 1 and not plus_plus:
+    if args.full and world > 1 and not plus_plus:
         other = build_rank(args.locality, "allgather" if args.exchange == "halo" else "halo")
         diff = (other["step"]() - R["step"]()).abs().max()
         dist.all_reduce(diff, op=dist.ReduceOp.MAX)
@@ -382,13 +422,65 @@ def main():
             raise SystemExit(f"halo and all-gather forms disagree: max |diff| = {exchange_check}")
         del other
 
+    # --- the headline line: the timed steps and the byte model of one forward, nothing re-measured
     result = None
+    b_alg = algorithmic_bytes(e_prime, n, c)
+    if rank == 0:
+        # the headline: B_fwd over the WHOLE forward as the driver times it (every launch of a step -
+        # normalise, main kernel, finalize - and the gaps between them): BASELINE.md's gate B_fwd / t_fwd
+        achieved = b_alg / (ms_per_step * 1e-3) / 1e9
+        layer = ("one SNGNN_Plus_Plus layer forward (adjacency branch + aggregation + blend)" if plus_plus
+                 else "SNGNN_Plus aggregation forward")
+        if world == 1:
+            parallelism = "single GPU"
+        else:
+            parallelism = ("node-range partition + RCCL " +
+                           ("halo exchange (all-to-all-v of the referenced rows, received into the [own | halo] "
+                            "table; interior rows aggregated while it is in flight)" if plan is not None
+                            else "all-gather of h") + (", w sharded by node range" if plus_plus else ""))
+        result = {
+            "metric": "similarity-aggregation edges/sec",
+            "value": e_all / (dt / args.steps),
+            "unit": "edges/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "preheat": {"ms": args.preheat_ms, "steps": preheat_steps,
+                        "what": "untimed steps in front of the warmup steps (the same step): a device coming out of idle runs "
+                                "its first ~15 ms ~7 % slower; cold_start (--full) = the same W + K measurement from an "
+                                "idle device"},
+            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"ogbn-{args.workload}-sized synthetic graph, {layer}, "
+                                   f"top_k={args.top_k}, thr={args.thr}, self-loops removed"
+                                   + (f", {args.locality:.0%} of a row's sources inside its rank's node range"
+                                      if world > 1 and not strong else ""),
+                       "nodes_per_gpu": n, "edges_per_gpu": e_prime, "channels": c,
+                       "parallelism": parallelism},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                         "what": "SURVEY.md 8d's algorithmic bytes of one forward over ms_per_step: the whole step "
+                                 "(normalise + main + finalize launches and the gaps), not one kernel of it; "
+                                 "the dominant kernel alone is priced under kernel_frac (--full)",
+                         "algorithmic_bytes": b_alg, "ms": ms_per_step},
+            # (the same figure under its round-3 name)
+            "roofline_step": {"bound": "hbm", "algorithmic_bytes": b_alg, "ms": ms_per_step,
+                              "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": achieved / HBM_PEAK_GBS},
+        }
+        if plus_plus:
+            # the whole ++ layer against its own byte model (SURVEY.md 8d, "++ branch extra")
+            b_pp = algorithmic_bytes(e_prime, n, c, plus_plus=True)
+            result["roofline_layer"] = {"bound": "hbm", "algorithmic_bytes": b_pp,
+                                        "achieved": b_pp / (ms_per_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                                        "unit": "GB/s", "frac": b_pp / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                        "what": "adjacency branch + aggregation + blend over the wall time of a step"}
+
     table = h_local
-    if world > 1:       # the local table of this rank, as the timed step sees it (a collective: every rank)
+    if args.full and world > 1:       # the local table of this rank, as the timed step sees it (a collective: every rank)
         with torch.no_grad():
             table = (sn_dist.halo_exchange(h_local, plan) if plan is not None
                      else sn_dist.all_gather_rows(h_local, R["part"]))
-    if rank == 0:
+    if args.full and rank == 0:
         # --- roofline leg: the dominant kernel's average launch duration, HIP events on its stream
         # around batches of 20 back-to-back launches (nothing subtracted); beside it the interval
         # of a single launch between two events (which carries the event pair's own ~4.5 us)
@@ -406,7 +498,6 @@ def main():
             lib.sngnn_tuning_set(9, 1)
             fin_ab = {"ms_per_step": dt0 / args.steps * 1e3, "normalize_kernel_ms": n0, "kernel_ms_batched_events": m0,
                       "finalize_kernel_ms": f0}
-        b_alg = algorithmic_bytes(e_prime, n, c)
         traffic = rocprof_us = traffic_src = None
         tpath = os.path.join(ROOT, "profiles", "traffic.json")
         if os.path.exists(tpath):
@@ -436,88 +527,42 @@ def main():
             main_ms = rocprof_us * 1e-3
             kernel_ms_source = "rocprofv3"
         kernel_achieved = b_alg / (main_ms * 1e-3) / 1e9
-        # the headline: B_fwd over the WHOLE forward as the driver times it (every launch of a step -
-        # normalise, main kernel, finalize - and the gaps between them): BASELINE.md's gate B_fwd / t_fwd
-        achieved = b_alg / (ms_per_step * 1e-3) / 1e9
-        layer = ("one SNGNN_Plus_Plus layer forward (adjacency branch + aggregation + blend)" if plus_plus
-                 else "SNGNN_Plus aggregation forward")
-        if world == 1:
-            parallelism = "single GPU"
-        else:
-            parallelism = ("node-range partition + RCCL " +
-                           ("halo exchange (all-to-all-v of the referenced rows, received into the [own | halo] "
-                            "table; interior rows aggregated while it is in flight)" if plan is not None
-                            else "all-gather of h") + (", w sharded by node range" if plus_plus else ""))
-        result = {
-            "metric": "similarity-aggregation edges/sec",
-            "value": e_all / (dt / args.steps),
-            "unit": "edges/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "preheat": {"ms": args.preheat_ms, "steps": preheat_steps,
-                        "what": "untimed steps in front of the warmup steps (the same step): a device coming out of idle runs "
-                                "its first ~15 ms ~7 % slower; cold_start = the same W + K measurement from an idle device"},
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"ogbn-{args.workload}-sized synthetic graph, {layer}, "
-                                   f"top_k={args.top_k}, thr={args.thr}, self-loops removed"
-                                   + (f", {args.locality:.0%} of a row's sources inside its rank's node range"
-                                      if world > 1 and not strong else ""),
-                       "nodes_per_gpu": n, "edges_per_gpu": e_prime, "channels": c,
-                       "parallelism": parallelism},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "what": "SURVEY.md 8d's algorithmic bytes of one forward over ms_per_step: the whole step "
-                                 "(normalise + main + finalize launches and the gaps), not one kernel of it; "
-                                 "the dominant kernel alone is priced under kernel_frac",
-                         "algorithmic_bytes": b_alg, "ms": ms_per_step,
-                         "kernel": "k_agg_fwd", "kernel_ms": main_ms, "kernel_ms_source": kernel_ms_source,
-                         "kernel_achieved": kernel_achieved, "kernel_frac": kernel_achieved / HBM_PEAK_GBS,
-                         "gather_floor_ms": floor_ms, "gather_floor_edges_only_ms": floor_edges_ms,
-                         "kernel_over_floor": None if not floor_ms else main_batched_ms / floor_ms,
-                         "gather_floor_what": "sngnn_gather_floor on this graph and table, this box, batched events like "
-                                              "kernel_ms_batched_events: every row read and row store of B_fwd (one 4C-byte row "
-                                              "per entry of the column list in CSR order, own row in, output row out) with no "
-                                              "arithmetic, no selection, no second fetch of kept rows; edges_only = the column "
-                                              "list's gather alone.  kernel_over_floor = kernel_ms_batched_events / gather_floor_ms",
-                         "normalize_floor_ms": copy_ms,
-                         "step_over_floors": None if not floor_ms else ms_per_step / (floor_ms + copy_ms),
-                         "floors_what": "normalize_floor_ms = a plain device copy of the table (the normalisation pass's bytes, no "
-                                        "arithmetic; torch copy_, batched events); step_over_floors = ms_per_step / (gather_floor_ms + "
-                                        "normalize_floor_ms): the whole step against the two measured floors of its two passes, "
-                                        "launch boundaries not counted",
-                         "normalize_kernel_ms": norm_ms, "finalize_kernel_ms": fin_ms,
-                         "finalize_workgroups_in_main": fin_wgs,
-                         "finalize_what": ("the split rows (in-degree > 128) are finalized by the last workgroups of the main "
-                                           "launch, each row as soon as its tasks have published their candidates: kernel_ms "
-                                           "holds that work, finalize_kernel_ms is an empty interval; "
-                                           "finalize_as_a_launch = the same step with sngnn_tuning_set(9, 0)") if fin_wgs > 0
-                         else "the split rows' finalize is the launch behind the main kernel",
-                         "finalize_as_a_launch": fin_ab,
-                         "launches_ms_sum": norm_ms + main_batched_ms + fin_ms,
-                         "kernel_ms_batched_events": main_batched_ms,
-                         "timer": "kernel_ms = max(HIP events on the launch stream around batches of 20 back-to-back "
-                                  "launches recorded inside the library: interval / 20, nothing subtracted; the committed "
-                                  "rocprofv3 --kernel-trace average of this command) - kernel_ms_source names the one used",
-                         "kernel_ms_single_launch_events": main_single_ms,
-                         "kernel_frac_single_launch_events": b_alg / (main_single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "empty_event_interval_ms": empty_ms,
-                         "kernel_ms_rocprofv3": None if rocprof_us is None else rocprof_us * 1e-3,
-                         "kernel_frac_rocprofv3": None if rocprof_us is None
-                         else b_alg / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS},
-            # (the same figure under its round-3 name)
-            "roofline_step": {"bound": "hbm", "algorithmic_bytes": b_alg, "ms": ms_per_step,
-                              "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": achieved / HBM_PEAK_GBS},
-        }
-        if plus_plus:
-            # the whole ++ layer against its own byte model (SURVEY.md 8d, "++ branch extra")
-            b_pp = algorithmic_bytes(e_prime, n, c, plus_plus=True)
-            result["roofline_layer"] = {"bound": "hbm", "algorithmic_bytes": b_pp,
-                                        "achieved": b_pp / (ms_per_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                                        "unit": "GB/s", "frac": b_pp / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                        "what": "adjacency branch + aggregation + blend over the wall time of a step"}
+        result["roofline"].update({
+            "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": "k_agg_fwd", "kernel_ms": main_ms, "kernel_ms_source": kernel_ms_source,
+            "kernel_achieved": kernel_achieved, "kernel_frac": kernel_achieved / HBM_PEAK_GBS,
+            "gather_floor_ms": floor_ms, "gather_floor_edges_only_ms": floor_edges_ms,
+            "kernel_over_floor": None if not floor_ms else main_batched_ms / floor_ms,
+            "gather_floor_what": "sngnn_gather_floor on this graph and table, this box, batched events like "
+                                 "kernel_ms_batched_events: every row read and row store of B_fwd (one 4C-byte row "
+                                 "per entry of the column list in CSR order, own row in, output row out) with no "
+                                 "arithmetic, no selection, no second fetch of kept rows; edges_only = the column "
+                                 "list's gather alone.  kernel_over_floor = kernel_ms_batched_events / gather_floor_ms",
+            "normalize_floor_ms": copy_ms,
+            "step_over_floors": None if not floor_ms else ms_per_step / (floor_ms + copy_ms),
+            "floors_what": "normalize_floor_ms = a plain device copy of the table (the normalisation pass's bytes, no "
+                           "arithmetic; torch copy_, batched events); step_over_floors = ms_per_step / (gather_floor_ms + "
+                           "normalize_floor_ms): the whole step against the two measured floors of its two passes, "
+                           "launch boundaries not counted",
+            "normalize_kernel_ms": norm_ms, "finalize_kernel_ms": fin_ms,
+            "finalize_workgroups_in_main": fin_wgs,
+            "finalize_what": ("the split rows (in-degree > 128) are finalized by the last workgroups of the main "
+                              "launch, each row as soon as its tasks have published their candidates: kernel_ms "
+                              "holds that work, finalize_kernel_ms is an empty interval; "
+                              "finalize_as_a_launch = the same step with sngnn_tuning_set(9, 0)") if fin_wgs > 0
+            else "the split rows' finalize is the launch behind the main kernel",
+            "finalize_as_a_launch": fin_ab,
+            "launches_ms_sum": norm_ms + main_batched_ms + fin_ms,
+            "kernel_ms_batched_events": main_batched_ms,
+            "timer": "kernel_ms = max(HIP events on the launch stream around batches of 20 back-to-back "
+                     "launches recorded inside the library: interval / 20, nothing subtracted; the committed "
+                     "rocprofv3 --kernel-trace average of this command) - kernel_ms_source names the one used",
+            "kernel_ms_single_launch_events": main_single_ms,
+            "kernel_frac_single_launch_events": b_alg / (main_single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "empty_event_interval_ms": empty_ms,
+            "kernel_ms_rocprofv3": None if rocprof_us is None else rocprof_us * 1e-3,
+            "kernel_frac_rocprofv3": None if rocprof_us is None
+            else b_alg / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBS})
     if world > 1:
         full = (n * world - n) * c * 4
         exch = {"form": args.exchange, "locality": args.locality,
@@ -530,7 +575,7 @@ def main():
         if rank == 0:
             result["exchange"] = exch
         # the same job on a graph with locality (what a node-range partition is for): second line
-        if not strong and args.locality != 0.8:
+        if args.full and not strong and args.locality != 0.8:
             R2 = build_rank(0.8, args.exchange)
             dt2, e2, halo2, _ = measure(R2, args.steps, max(args.warmup // 2, 2))
             if rank == 0:
@@ -543,7 +588,7 @@ def main():
             del R2
 
     # --- extras on one GPU
-    if world == 1 and rank == 0 and not plus_plus:
+    if args.full and world == 1 and rank == 0 and not plus_plus:
         # BASELINE.md's other config-4 cases, timed the same way inside this run
         if not args.no_variants and args.workload == "arxiv" and args.channels is None:
             variants = {}
@@ -667,9 +712,9 @@ def main():
             # the benchmarked output is the checked output
             err = (out.cpu() - res["out"]).abs().max().item()
             result["max_abs_err_vs_oracle"] = err
-    if world == 1 and rank == 0 and plus_plus:
+    if args.full and world == 1 and rank == 0 and plus_plus:
         result.update(products_training(ops, graph, R, args, e_prime, n, c))
-    if world == 1 and rank == 0 and args.preheat_ms > 0:
+    if args.full and world == 1 and rank == 0 and args.preheat_ms > 0:
         # the same W + K measurement from an idle device (the CPU baseline above left it idle for ~a second; a short
         # sleep for the runs that skipped it)
         torch.cuda.synchronize()

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_single_gpu_line(cuda):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-           "--no-epoch", "--no-variants"]
+           "--full", "--no-epoch", "--no-variants"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -51,3 +51,34 @@ def test_single_gpu_line(cuda):
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == d["unit"]
     assert d["value"] > 100 * cb["value"]
     assert d["max_abs_err_vs_oracle"] < 1e-5
+
+
+def test_plain_line_and_dumped_outputs(cuda, tmp_path):
+    """The plain run (no --full): the headline keys only, and --dump-outputs writes the last timed step's output -
+    the same rows the oracle computes from the same seeded inputs."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import sngnn_oracle as O
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+           "--dump-outputs", str(tmp_path)]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["unit"] == "edges/s"
+    assert abs(d["value"] - d["config"]["edges_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert abs(d["roofline"]["achieved"] - d["roofline"]["algorithmic_bytes"] / (d["ms_per_step"] * 1e-3) / 1e9) \
+        <= 1e-6 * d["roofline"]["achieved"]
+    for key in ("cpu_baseline", "cold_start", "fwd_bwd_ms", "roofline_bwd", "variants", "epoch_ms"):
+        assert key not in d, key          # --full only
+    assert "kernel_ms" not in d["roofline"]
+    assert sorted(os.listdir(tmp_path)) == ["out.npy"]
+    got = np.load(tmp_path / "out.npy")
+    n, c = d["config"]["nodes_per_gpu"], d["config"]["channels"]
+    assert got.dtype == np.float32 and got.shape == (n, c)
+    _, _, ei, _, h, _ = bench.make_rank_inputs("arxiv", 0, 1, 1234, cuda)
+    want = O.aggregate_reference(h.cpu(), ei.cpu(), add_loops=True, remove_loops=True, top_k=16, thr=0.0)["out"]
+    assert np.abs(got - want.numpy()).max() < 1e-5

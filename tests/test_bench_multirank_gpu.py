@@ -16,7 +16,7 @@ def test_two_rank_rehearsal(cuda):
     env = dict(os.environ, SNGNN_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.05", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.05", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -39,7 +39,7 @@ def test_two_rank_rehearsal_of_the_products_workload(cuda):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--workload", "products", "--steps", "2", "--warmup", "1", "--scale", "0.01",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -148,25 +148,34 @@ def test_geom_gcn_parser(tmp_path, index_features):
     assert s.train_mask.tolist() == [True, False, False, False] and s.x is d.x
 
 
-def test_actor_fixture_statistics():
+def test_actor_fixture_statistics(tmp_path):
     """tests/golden/actor_topology.npz was parsed from the raw files the reference
     bundles (datasets/data/Actor/raw); its statistics are the ones SURVEY.md row 13
-    measured independently."""
+    measured independently.  The raw files themselves (split 0 of ten) are stored
+    gzipped under tests/golden/actor_raw/ and re-parsed here."""
+    import gzip
     import os
+    import shutil
     import numpy as np
-    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "actor_topology.npz"))
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    z = np.load(os.path.join(golden, "actor_topology.npz"))
     n, e, loops, max_deg, zero_deg, f, classes = (int(v) for v in z["stats"])
     assert (n, e, loops, max_deg, zero_deg, f, classes) == (7600, 30019, 93, 1296, 2236, 932, 5)
     ei = z["edge_index"].astype(np.int64)
     assert ei.shape == (2, e) and (np.diff(ei[0] * n + ei[1]) > 0).all()
     assert (int(z["train_mask0"].sum()), int(z["val_mask0"].sum()), int(z["test_mask0"].sum())) == \
         (3648, 2432, 1520)
-    raw = "/root/reference/datasets/data/Actor/raw"
-    if os.path.isdir(raw):                                  # where the reference is mounted: re-parse
-        from sngnn_amd import datasets as DS
-        d = DS.load_geom_gcn(raw, "film")
-        assert np.array_equal(d.edge_index.numpy(), ei) and d.x.shape == (n, f)
-        assert np.array_equal(d.y.numpy(), z["y"].astype(np.int64))
+    src = os.path.join(golden, "actor_raw")
+    for name in ("out1_graph_edges.txt", "out1_node_feature_label.txt"):
+        with gzip.open(os.path.join(src, name + ".gz"), "rb") as fi, open(tmp_path / name, "wb") as fo:
+            shutil.copyfileobj(fi, fo)
+    shutil.copy(os.path.join(src, "film_split_0.6_0.2_0.npz"), tmp_path)
+    from sngnn_amd import datasets as DS
+    d = DS.load_geom_gcn(str(tmp_path), "film")
+    assert np.array_equal(d.edge_index.numpy(), ei) and d.x.shape == (n, f)
+    assert np.array_equal(d.y.numpy(), z["y"].astype(np.int64))
+    assert np.array_equal(d.train_mask[0].numpy(), z["train_mask0"]) and np.array_equal(d.val_mask[0].numpy(), z["val_mask0"])
+    assert np.array_equal(d.test_mask[0].numpy(), z["test_mask0"])
 
 
 def test_ogb_raw_layout_loader(tmp_path):

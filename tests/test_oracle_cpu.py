@@ -4,6 +4,8 @@ restatement."""
 import glob
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -203,18 +205,30 @@ def _t(a):
     return torch.from_numpy(np.asarray(a))
 
 
-def test_oracle_toolbox_dense_small_fixture_bit_exact():
+def _dense_small_fixture_mismatches():
+    """The entries of toolbox_dense_small.npz that the oracle's restatement does not reproduce bit for bit."""
     z = _z("toolbox_dense_small.npz")
     x, ei, y = _t(z["x"]), _t(z["edge_index"]), _t(z["y"])
-    assert torch.equal(O.cosine_similarity_dense_small(x), _t(z["cosine"]))
-    for got, key in zip(O.node_similarity_dense_small(x), ("node_sim", "node_mean")):
-        assert torch.equal(got, _t(z[key])), key
-    for got, key in zip(O.linked_node_similarity_dense_small(x, ei), ("linked_sim", "linked_mean")):
-        assert torch.equal(got, _t(z[key])), key
-    for got, key in zip(O.neighborhood_similarity_dense_small(x, ei), ("nbr_weight", "nbr_mean")):
-        assert torch.equal(got, _t(z[key])), key
-    for got, key in zip(O.class_similarity_dense_small(x, y), ("class_mat", "class_mean")):
-        assert torch.equal(got, _t(z[key])), key
+    bad = [] if torch.equal(O.cosine_similarity_dense_small(x), _t(z["cosine"])) else ["cosine"]
+    for fn, args, keys in ((O.node_similarity_dense_small, (x,), ("node_sim", "node_mean")),
+                           (O.linked_node_similarity_dense_small, (x, ei), ("linked_sim", "linked_mean")),
+                           (O.neighborhood_similarity_dense_small, (x, ei), ("nbr_weight", "nbr_mean")),
+                           (O.class_similarity_dense_small, (x, y), ("class_mat", "class_mean"))):
+        bad += [key for got, key in zip(fn(*args), keys) if not torch.equal(got, _t(z[key]))]
+    return bad
+
+
+def test_oracle_toolbox_dense_small_fixture_bit_exact():
+    """Bit for bit.  S = normalize(x) @ normalize(x).T goes through MKL's sgemm, whose kernel - and with it the
+    last bits of S - depends on the host CPU; the fixture holds the bits of MKL's AVX2 branch, so the comparison
+    runs in a child process with that branch pinned (MKL_CBWR=AVX2,STRICT: MKL's conditional numerical
+    reproducibility, independent of the thread count; MKL reads it once, when it loads)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "from tests.test_oracle_cpu import _dense_small_fixture_mismatches as f; print('mismatches:', f())"
+    res = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, MKL_CBWR="AVX2,STRICT"),
+                         capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-3000:]
+    assert "mismatches: []" in res.stdout, res.stdout[-2000:]
 
 
 @pytest.mark.parametrize("name", ["toolbox_dense_small.npz", "toolbox_dense_parted.npz"])
