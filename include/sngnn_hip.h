@@ -631,6 +631,63 @@ int64_t sngnn_knn_workspace_bytes(int64_t N, int k);
 int sngnn_knn_graph(const float *x, int64_t N, int64_t F, int k, int exclude_self,
                     int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------
+ * R replicas of one 1-layer model trained together (sngnn_amd/splits.py): the sweep scripts'
+ * ten geom-gcn splits (train_script_SNGNN{,_plus,_plus_plus}.sh: part_id 0..9, one process each)
+ * and SNGNN++'s init_beta grid in one job.  Replica r's node i is row r N + i of a block-diagonal
+ * union graph (the aggregation entries above run on it unchanged); the entries below are the
+ * per-replica parts of lin, the head and the blend.  Every sum is fixed-order; none blocks the host.
+ * ------------------------------------------------------------------------ */
+/*
+ * Replaces: R separate `self.lin(x)` bias adds and F.normalize passes (models.py:121-122, 237-238,
+ * 324-325, one process per split).  hs dev f32 [N, R C] = x W_stacked^T (one GEMM over the stacked
+ * [R C, F] weights: x read once); bias dev f32 [R, C] or NULL.  Writes the union table
+ * h [R N, C] (row r N + i = hs[i, r C .. r C + C) + bias[r]) and, n / nrm non-NULL, the unit rows,
+ * the clamped norms and (filt non-NULL) the fp16 filter rows - bit for bit what
+ * sngnn_normalize_rows_filter computes from h - in the same pass.
+ */
+int sngnn_replica_unpack(const float *hs, const float *bias, int64_t N, int R, int C, float *h, float *n,
+                         float *nrm, void *filt, void *stream);
+/*
+ * Replaces: R calls of sngnn_linear_wgrad (autograd of self.lin, models.py:121,237,324 - one per split's
+ * process): grad_weight [R C, F] (block r = G_r^T x), grad_bias [R C] (may be NULL), G = grad_out dev f32
+ * [R N, C] in the union layout, x read once per 64 stacked channels.  Per element the summation order of
+ * sngnn_linear_wgrad's FMA path (the one it takes unless F is 16, 32, 64 or 128 and N >= 1024):
+ * replica r's result equals that call on G_r bit for bit there.
+ * workspace: sngnn_replica_wgrad_workspace_bytes(N, R, C, F).
+ */
+int64_t sngnn_replica_wgrad_workspace_bytes(int64_t N, int R, int C, int F);
+int sngnn_replica_wgrad(const float *grad_out, const float *x, int64_t N, int R, int C, int F,
+                        float *grad_weight, float *grad_bias, void *workspace, void *stream);
+/*
+ * Replaces: per split's process, log_softmax (models.py:86,211,303) + nll_loss on the split's rows +
+ * the accuracy count (train.py:81-84, 98-102, 112-116).  logits dev f32 [R N, C] (C <= 64); with
+ * logits1 / beta dev f32 [R] non-NULL the logits are SNGNN++'s blend beta[r] logits + (1 - beta[r])
+ * logits1 (models.py:134) formed in registers.  y dev i64 [N] (shared); sel dev u8 [R, N]: sets = 1,
+ * nonzero = the replica's split; sets = 2, bit 0 / bit 1 = splits A / B.  counts dev i64 [R sets]: the
+ * rows of each split (the mean's divisor).  metrics row r (at metrics + r metrics_stride) = {loss,
+ * correct} per split.  grad_logits (sets == 1, or NULL) [R N, C]: d (mean NLL_r) / d logits.
+ * Replica r's results equal sngnn_head_nll / _nll2 / _nll_blend on its rows bit for bit.
+ * workspace: sngnn_replica_head_workspace_bytes(R).
+ */
+int64_t sngnn_replica_head_workspace_bytes(int R);
+int sngnn_replica_head_nll(const float *logits, const float *logits1, const float *beta, const int64_t *y,
+                           const unsigned char *sel, const int64_t *counts, int64_t N, int R, int C, int sets,
+                           float *grad_logits, float *metrics, int64_t metrics_stride, void *workspace,
+                           void *stream);
+/*
+ * Replaces: R calls of sngnn_blend_forward / _backward (models.py:134) with one beta per replica:
+ * n elements per replica, replica r's slice at offset r n; grad_beta dev f32 [R].  Per replica the grid
+ * and reduction tree of the single call (bit for bit when n % 4 == 0).
+ * workspace: sngnn_replica_blend_workspace_bytes(R).
+ */
+int64_t sngnn_replica_blend_workspace_bytes(int R);
+int sngnn_replica_blend_forward(const float *out0, const float *out1, const float *beta, int64_t n, int R,
+                                float *out, void *stream);
+int sngnn_replica_blend_backward(const float *grad_out, const float *out0, const float *out1,
+                                 const float *beta, int64_t n, int R, float *grad0, float *grad1,
+                                 float *grad_beta, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

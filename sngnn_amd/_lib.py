@@ -100,6 +100,15 @@ SIGNATURES = {
     "sngnn_edge_cosine": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "sngnn_segment_mean": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sngnn_sparse_pair_dot": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "sngnn_replica_unpack": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_replica_wgrad_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "sngnn_replica_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_replica_head_workspace_bytes": (_i64, [_i32]),
+    "sngnn_replica_head_nll": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp,
+                                      _vp]),
+    "sngnn_replica_blend_workspace_bytes": (_i64, [_i32]),
+    "sngnn_replica_blend_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "sngnn_replica_blend_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

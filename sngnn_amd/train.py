@@ -110,6 +110,12 @@ class GraphedEpoch:
         self.fused_head = (self.fused and hasattr(model, "forward_head")
                            and os.environ.get("SNGNN_FUSE_HEAD", "1") == "1")
         self.metrics = torch.zeros(6, dtype=torch.float32, device=dev)
+        self._prepare_optimizer()
+        self._capture(warmup)
+
+    def _prepare_optimizer(self):
+        """Adam ``capturable`` (fused where it applies) with its state created up front."""
+        optimizer = self.opt
         for g in optimizer.param_groups:
             g["capturable"] = True
             # one multi-tensor kernel per step instead of ~10 small ones per parameter (same
@@ -123,6 +129,12 @@ class GraphedEpoch:
                     and all(dense(p) and p.is_cuda for p in g["params"])):
                 g["fused"] = True
         self._materialise_adam_state()
+
+    def _capture(self, warmup: int):
+        """Priming forward and ``warmup`` eager epochs on a side stream, then :meth:`_epoch` captured
+        once into ``self.graph`` (the graphs its launches use are kept alive in ``self._held_graphs``)."""
+        model, data = self.model, self.data
+        dev = data.x.device
         if hasattr(model, "prepare_capture"):
             # host-side lazy state of a training forward (the in-kernel dropout's seed counters) must
             # exist before the capture: with warmup=0 the first training forward IS the captured one
