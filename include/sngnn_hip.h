@@ -335,6 +335,34 @@ int sngnn_agg_backward_bits(const sngnn_graph_t *g, const float *h, int C, const
                             const void *kept_bits, int top_k, float *grad_h, void *workspace, void *stream);
 
 /*
+ * Half-width feature rows: the aggregation on fp16 or bf16 h, forward and backward.
+ * Replaces the same reference lines as sngnn_agg_forward / sngnn_agg_backward_topk (models.py:122+132+139-158,
+ * :238-239+244-263, :325-326+331-334 and autograd through them, train.py:86) for a model cast to
+ * torch.float16 / torch.bfloat16 - but NOT their eager arithmetic in that type, which would round the unit rows and
+ * the cosines to 11 or 8 bits and create spurious ties.  Contract, with hf = h widened to fp32 (exact):
+ *   forward:  the fp32 operator on hf, scoring on the fly (sngnn_tuning_set(2, 2): sngnn_agg_forward scores the
+ *             raw rows, no unit-row table), with only `out` rounded once to the storage type (round to nearest
+ *             even).  wsel, inv_norm, sel_src and sel_w stay fp32 and equal that call's bit for bit, exact ties
+ *             included; the kept edges are those of the default sngnn_agg_forward on hf.
+ *   backward: sngnn_agg_backward_topk(hf, grad_out widened, wsel, top_k) rounded once to the storage type.
+ * The kernels are the fp32 ones with their row loads and output stores in the storage type (same lanes, same
+ * summation order; norms, cosines and sums in fp32); deterministic, no floating-point atomics, no host sync.
+ *   dtype    SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16: the type of h, out, grad_out and grad_h (anything else:
+ *            SNGNN_EINVAL)
+ *   h, out, grad_out, grad_h   dev, that type, rows of C values aligned to 2 * vec bytes (vec = 4, 2 or 1 for
+ *            C % 4 == 0, C % 2 == 0, odd C: the fp32 layout's values per lane)
+ *   workspace  sngnn_graph_workspace_bytes(g, C) bytes (an upper bound: the half path uses less)
+ * No store epilogue, head, filter rows or kept bits: the caller runs those steps in torch.
+ */
+#define SNGNN_DTYPE_F16 1
+#define SNGNN_DTYPE_BF16 2
+int sngnn_agg_forward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, int top_k, float thr,
+                           void *out, float *wsel, float *inv_norm, int32_t *sel_src, float *sel_w,
+                           void *workspace, void *stream);
+int sngnn_agg_backward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, const void *grad_out,
+                            const float *wsel, int top_k, void *grad_h, void *workspace, void *stream);
+
+/*
  * Cosine-attention mode of the same gather skeleton.
  * Replaces: AGNNConv.forward after ``lin`` + message + aggr='add'
  * (models.py:396-405): alpha_e = softmax over the in-edges of target i of

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNGNN_LIB_PATH") or os.path.join(_HERE, "libsngnn_hip.so")
 
 OK, EINVAL, ERANGE, EHIP, ENOMEM = 0, -1, -2, -3, -4
+DTYPE_F16, DTYPE_BF16 = 1, 2          # SNGNN_DTYPE_*: storage types of the half path's rows
 UNSELECTED = -4.0
 MAX_CHANNELS = 512
 
@@ -61,6 +62,8 @@ SIGNATURES = {
     "sngnn_agg_head_workspace_bytes": (_i64, [_vp]),
     "sngnn_graph_kept_bits_bytes": (_i64, [_vp]),
     "sngnn_agg_backward_bits": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "sngnn_agg_forward_half": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_agg_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_attn_forward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_attn_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_signed_forward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

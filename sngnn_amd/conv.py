@@ -67,6 +67,7 @@ def _graph_for(x: torch.Tensor, edge_index: torch.Tensor, add_loops: bool, remov
     part = sn_dist.current_partition()
     if part is None:
         return GLOBAL_CACHE.get(edge_index, x.size(0), add_loops, remove_loops), None
+    sn_dist.check_features(x)
     if x.size(0) != part.n_local:
         raise ValueError(f"under a partition x must be the rank's {part.n_local} rows, got {x.size(0)}")
     shard = _shard_for(edge_index, part, add_loops, remove_loops)
@@ -231,6 +232,47 @@ def _aggregate(h: torch.Tensor, graph, shard, top_k, thr: float, table=None, uni
     return ops.aggregate(shard.table(h), graph, top_k, thr)
 
 
+# ---- the half path: a model and its features cast to float16 / bfloat16 -------------------------------------------
+# ``lin`` is torch's F.linear, the aggregation the library's half kernels (ops.aggregate on a half h: the fp32
+# operator on h.float(), only its output rounded to the type), the bias and the blend run in torch; no unit rows,
+# filter rows, store epilogue or head.  HALF_PAD: the half rows are padded with zero channels up to the width their
+# own 16-byte lane layout spans anyway (4 G R channels, row_cfg in csrc/common.h: 40 -> 64, 48 -> 64) - the same
+# lanes then hold the same zeros, so no bit changes, and a row is whole 128-byte lines.  Set by measurement
+# (tools/bench_half.py).
+HALF_PAD = False
+
+
+def half_width(c: int) -> int:
+    """Channels a half row of ``c`` channels is stored with (HALF_PAD; C % 4 == 0 only: other widths keep the
+    narrower layout, whose sums a padded row would reorder)."""
+    if not HALF_PAD or c % 4 != 0:
+        return c
+    lanes, g = c // 4, 8
+    while g < lanes and g < 64:
+        g <<= 1
+    r, rr = -(-lanes // g), 1
+    while rr < r:
+        rr <<= 1
+    return 4 * g * rr
+
+
+def _half_conv(x, edge_index, lin, add_loops, remove_loops, top_k, thr, epilogue=None, head=None, fold=None):
+    """(mean aggregation of lin(x) in x's half dtype, graph) - see HALF_PAD's note."""
+    if epilogue is not None:
+        epilogue.applied = False
+    if head is not None:
+        head.applied = False
+    graph, _ = _graph_for(x, edge_index, add_loops, remove_loops)       # (a partition refuses half features)
+    c = lin.out_features
+    weight, bias = (lin.weight, lin.bias) if fold is None else fold.apply(lin)
+    cp = half_width(c)
+    if cp != c:
+        weight = F.pad(weight, (0, 0, 0, cp - c))
+        bias = None if bias is None else F.pad(bias, (0, cp - c))
+    h = F.linear(x, weight, bias)
+    return _true_width(ops.aggregate(h, graph, top_k, thr), c), graph
+
+
 class SNConv(nn.Module):
     """models.py:305-334: self-loops added (never removed), every in-edge weighted
     by its cosine, mean over the full in-degree, ``bias=True`` by default."""
@@ -257,6 +299,9 @@ class SNConv(nn.Module):
         (ops.HiddenEpilogue).  ``epilogue.applied`` says whether the layer did.  ``head`` (the LAST
         layer): the classification head inside the aggregation's launches (ops.HeadEpilogue; ``head.applied``).
         ``fold``: a ``LinFold`` - an evaluation-mode batch norm in front of this layer, folded into ``lin``."""
+        if x.dtype in ops.HALF_DTYPES:
+            out, _ = _half_conv(x, edge_index, self.lin, True, False, None, 0.0, epilogue, head, fold)
+            return out if self.bias is None else out + self.bias
         graph, shard = _graph_for(x, edge_index, True, False)
         # (no selection: the aggregation scores straight from h - no unit rows wanted from lin)
         h, c, table = _lin_aligned(x, self.lin, shard, None, act_in, fold)
@@ -327,6 +372,10 @@ class SNConv_plus(nn.Module):
 
     def forward(self, x, edge_index, epilogue=None, act_in=None, head=None, fold=None):
         """``epilogue`` / ``act_in`` / ``head`` / ``fold``: see SNConv.forward."""
+        if x.dtype in ops.HALF_DTYPES:
+            out, _ = _half_conv(x, edge_index, self.lin, True, bool(self.is_remove_self_loops), int(self.top_k),
+                                float(self.thr), epilogue, head, fold)
+            return out if self.bias is None else out + self.bias
         graph, shard = _graph_for(x, edge_index, True, bool(self.is_remove_self_loops))
         hint = self._filter_hint()
         hint.poll()
@@ -506,6 +555,15 @@ class SNConv_plus_plus(nn.Module):
                              "(the adjacency branch is Linear(num_nodes, C))")
         if part is None and self.w.shard_range is not None:
             raise ValueError("this layer holds a shard of w (built under a partition): run it under one")
+        if x.dtype in ops.HALF_DTYPES:
+            # the half path: the adjacency branch is the fp32 kernel on an fp32 copy of w (its rows are gathered,
+            # not normalised: no half kernel of its own), cast back; the blend in torch (models.py:134)
+            out_1, graph = _half_conv(x, edge_index, self.lin, True, bool(self.is_remove_self_loops), int(self.top_k),
+                                      float(self.thr), None, None, fold)
+            wb = self.w.bias
+            out_0 = ops.adj_linear(self.w.weight.float(), None if wb is None else wb.float(), graph).to(x.dtype)
+            out = self.beta * out_0 + (1 - self.beta) * out_1
+            return out if self.bias is None else out + self.bias
         graph, shard = _graph_for(x, edge_index, True, bool(self.is_remove_self_loops))
         hint = self._filter_hint()
         hint.poll()

@@ -31,7 +31,8 @@ bool sngnn::kept_bits_path(const sngnn_graph_t *g, int top_k)
 }
 
 static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const float *grad_out, const float *wsel,
-                         const unsigned *kbits, int top_k, float *grad_h, void *workspace, void *stream);
+                         const unsigned *kbits, int top_k, float *grad_h, void *workspace, void *stream,
+                         int dtype = 0);
 
 extern "C" int sngnn_agg_backward_topk(const sngnn_graph_t *g, const float *h, int C,
                                        const float *grad_out, const float *wsel, int top_k,
@@ -51,8 +52,19 @@ extern "C" int sngnn_agg_backward_bits(const sngnn_graph_t *g, const float *h, i
     return backward_impl(g, h, C, grad_out, nullptr, (const unsigned *)kept_bits, top_k, grad_h, workspace, stream);
 }
 
+// the half path: h, grad_out and grad_h stored as fp16 / bf16 (everything else as in sngnn_agg_backward_topk)
+extern "C" int sngnn_agg_backward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, const void *grad_out,
+                                       const float *wsel, int top_k, void *grad_h, void *workspace, void *stream)
+{
+    SN_REQUIRE(dtype == SNGNN_DTYPE_F16 || dtype == SNGNN_DTYPE_BF16, SNGNN_EINVAL,
+               "dtype must be SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16");
+    SN_REQUIRE(g == nullptr || wsel != nullptr || g->Ep == 0, SNGNN_EINVAL, "wsel is NULL");
+    return backward_impl(g, (const float *)h, C, (const float *)grad_out, wsel, nullptr, top_k, (float *)grad_h,
+                         workspace, stream, dtype);
+}
+
 static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const float *grad_out, const float *wsel,
-                         const unsigned *kbits, int top_k, float *grad_h, void *workspace, void *stream)
+                         const unsigned *kbits, int top_k, float *grad_h, void *workspace, void *stream, int dtype)
 {
     SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
     if (g->Ntot == 0) return SNGNN_OK;
@@ -60,7 +72,7 @@ static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const fl
     RowCfg cfg;
     SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL,
                "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    const uintptr_t al = (uintptr_t)cfg.vec * 4;
+    const uintptr_t al = (uintptr_t)cfg.vec * (dtype != 0 ? 2 : 4);     // (half rows: 2 bytes a value)
     SN_REQUIRE((uintptr_t)h % al == 0 && (uintptr_t)grad_out % al == 0 && (uintptr_t)grad_h % al == 0,
                SNGNN_EINVAL, "h/grad_out/grad_h must be aligned to the row vector width");
     BwdArgs a;
@@ -102,6 +114,14 @@ static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const fl
     a.kbits = kbits; a.csc_bit = g->csc_bit; a.kb_wbase = (int)g->kb_wbase; a.kb_tbase = (int)g->kb_tbase;
     a.s_small_end = a.mode == 0 ? g->srcs_gt(SMALL_T - 1) : (int)g->Ntot;
     hipStream_t st = (hipStream_t)stream;
+    if (dtype != 0) {
+        const bool f16 = dtype == SNGNN_DTYPE_F16;
+        switch (cfg.vec) {
+        case 1: return f16 ? launch_agg_bwd_f16_v1(cfg, a, st) : launch_agg_bwd_bf16_v1(cfg, a, st);
+        case 2: return f16 ? launch_agg_bwd_f16_v2(cfg, a, st) : launch_agg_bwd_bf16_v2(cfg, a, st);
+        default: return f16 ? launch_agg_bwd_f16_v4(cfg, a, st) : launch_agg_bwd_bf16_v4(cfg, a, st);
+        }
+    }
     switch (cfg.vec) {
     case 1: return launch_agg_bwd_v1(cfg, a, st);
     case 2: return launch_agg_bwd_v2(cfg, a, st);

@@ -74,6 +74,12 @@ struct BwdArgs {
     const unsigned *kbits;
     const int32_t *csc_bit;
     int kb_wbase, kb_tbase;
+    // h, gout and grad_h in their storage type S (the kernels' template parameter): float, or __half /
+    // __hip_bfloat16 for the half path (sngnn_agg_backward_half).  The scratch rows dnT / partT / partS, the
+    // weights and the kept bits stay fp32 / unchanged.
+    template <typename S> __device__ __forceinline__ const S *hrows() const { return reinterpret_cast<const S *>(h); }
+    template <typename S> __device__ __forceinline__ const S *grows() const { return reinterpret_cast<const S *>(gout); }
+    template <typename S> __device__ __forceinline__ S *dhrows() const { return reinterpret_cast<S *>(grad_h); }
 };
 
 __device__ __forceinline__ bool kbit(const BwdArgs &a, int b) { return (a.kbits[b >> 5] >> (b & 31)) & 1u; }
@@ -160,7 +166,7 @@ __device__ __forceinline__ int kept_list(const BwdArgs &a, int rs, int e0, int e
 // small targets (deg <= SMALL_T), one group per row.  The group's lanes first fetch the
 // kept flags and source ids of all its edges in parallel (one round trip), then the
 // kept source rows are gathered two at a time.
-template <int VEC, int G, int R, bool MARK>
+template <int VEC, int G, int R, bool MARK, typename S = float>
 __device__ __forceinline__ void t_role_small(const BwdArgs &a, int blk, int *lds_wave, const int4 *desc, int n_desc)
 {
     using RowT = Row<VEC, G, R>;
@@ -198,7 +204,7 @@ __device__ __forceinline__ void t_role_small(const BwdArgs &a, int blk, int *lds
         nk += __popcll(gm);
     }
     RowT gp, acc;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     gp.scale(invdeg);
     acc.zero();
     wave_lds_sync();
@@ -206,15 +212,15 @@ __device__ __forceinline__ void t_role_small(const BwdArgs &a, int blk, int *lds
         const bool two = q0 + 1 < nk;
         const int q1 = two ? q0 + 1 : q0;
         RowT x0, x1;
-        x0.load(a.h + (size_t)s_j[q0] * a.C, a.C, lg);
-        x1.load(a.h + (size_t)s_j[q1] * a.C, a.C, lg);
+        x0.load(a.hrows<S>() + (size_t)s_j[q0] * a.C, a.C, lg);
+        x1.load(a.hrows<S>() + (size_t)s_j[q1] * a.C, a.C, lg);
         t_edge_row<VEC, G, R>(x0, gp, acc);
         t_edge_row<VEC, G, R>(x1, gp, acc, two ? 1.0f : 0.0f);
     }
     acc.store(a.dnT + (size_t)i * a.C, a.C, lg);
 }
 
-template <int VEC, int G, int R, bool MARK>
+template <int VEC, int G, int R, bool MARK, typename S = float>
 __device__ __forceinline__ void t_role_wave(const BwdArgs &a, int blk, int *lds_wave, bool task)
 {
     using RowT = Row<VEC, G, R>;
@@ -239,7 +245,7 @@ __device__ __forceinline__ void t_role_wave(const BwdArgs &a, int blk, int *lds_
     e1 = task ? min(deg, e0 + CHUNK) : deg;
     RowT gp, acc;
     const float invdeg = 1.0f / (float)deg;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     gp.scale(invdeg);
     acc.zero();
     int *jlist = lds_wave;
@@ -251,8 +257,8 @@ __device__ __forceinline__ void t_role_wave(const BwdArgs &a, int blk, int *lds_
     for (int q0 = 0; q0 < nsel; q0 += 2 * NG) {
         const int qa = min(q0 + gid, nsel - 1), qb = min(q0 + NG + gid, nsel - 1);
         RowT xa, xb;
-        xa.load(a.h + (size_t)jlist[qa] * a.C, a.C, lg);
-        xb.load(a.h + (size_t)jlist[qb] * a.C, a.C, lg);
+        xa.load(a.hrows<S>() + (size_t)jlist[qa] * a.C, a.C, lg);
+        xb.load(a.hrows<S>() + (size_t)jlist[qb] * a.C, a.C, lg);
         t_edge_row<VEC, G, R>(xa, gp, acc, q0 + gid < nsel ? 1.0f : 0.0f);
         t_edge_row<VEC, G, R>(xb, gp, acc, q0 + NG + gid < nsel ? 1.0f : 0.0f);
     }
@@ -263,15 +269,15 @@ __device__ __forceinline__ void t_role_wave(const BwdArgs &a, int blk, int *lds_
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_bwd_t(const BwdArgs a)
 {
     __shared__ __align__(16) int lds[WAVES][WAVE_T];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
-    if (b < a.nbA) t_role_wave<VEC, G, R, true>(a, b, lw, true);
-    else if (b < a.nbA + a.nbB) t_role_wave<VEC, G, R, true>(a, b - a.nbA, lw, false);
-    else t_role_small<VEC, G, R, true>(a, b - a.nbA - a.nbB, lw, a.rdesc + a.n_med_end, a.N - a.n_med_end);
+    if (b < a.nbA) t_role_wave<VEC, G, R, true, S>(a, b, lw, true);
+    else if (b < a.nbA + a.nbB) t_role_wave<VEC, G, R, true, S>(a, b - a.nbA, lw, false);
+    else t_role_small<VEC, G, R, true, S>(a, b - a.nbA - a.nbB, lw, a.rdesc + a.n_med_end, a.N - a.n_med_end);
 }
 
 // split targets: dnT_i = sum of the tasks' partial rows.  Thread (c, q) adds every 4th
@@ -320,7 +326,7 @@ __device__ __forceinline__ void s_edge(const BwdArgs &a, int i, float2 rec, int 
 
 // the rows s_finish needs, requested at the START of an item so that they travel with the
 // item's first loads instead of adding a round trip at its end
-template <int VEC, int G, int R> struct FinishRows {
+template <int VEC, int G, int R, typename S = float> struct FinishRows {
     Row<VEC, G, R> t, hv;
     bool own;
     __device__ __forceinline__ void load(const BwdArgs &a, int v, int lg)
@@ -328,14 +334,14 @@ template <int VEC, int G, int R> struct FinishRows {
         const int vl = v - a.row_off;                 // owned nodes also carry a target part
         own = vl >= 0 && vl < a.N;
         t.load(a.dnT + (size_t)(own ? vl : 0) * a.C, a.C, lg);
-        hv.load(a.h + (size_t)v * a.C, a.C, lg);
+        hv.load(a.hrows<S>() + (size_t)v * a.C, a.C, lg);
     }
 };
 
 // dh_v from msg_v and dn_v = dnT_v + dnS_v
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void s_finish(const BwdArgs &a, int v, int lg, Row<VEC, G, R> &msg,
-                                         Row<VEC, G, R> &dn, FinishRows<VEC, G, R> &f)
+                                         Row<VEC, G, R> &dn, FinishRows<VEC, G, R, S> &f)
 {
     if (f.own) dn.add(f.t);
     Row<VEC, G, R> &hv = f.hv;
@@ -349,7 +355,7 @@ __device__ __forceinline__ void s_finish(const BwdArgs &a, int v, int lg, Row<VE
 #pragma unroll
         for (int c = 0; c < VEC; ++c)
             msg.x[r][c] += (dn.x[r][c] - hv.x[r][c] * proj) * invv;
-    msg.store(a.grad_h + (size_t)v * a.C, a.C, lg);
+    msg.store(a.dhrows<S>() + (size_t)v * a.C, a.C, lg);
 }
 
 // one kept out-edge (v -> i) from the rows alone: x = h_i, gi = G_i, hv = h_v (own, raw),
@@ -383,7 +389,7 @@ __device__ __forceinline__ void s_edge_rows(const Row<VEC, G, R> &x, const Row<V
 //   REC = true:  per-edge scalars from the records a.wd (attention mode)
 //   REC = false: kept bits from a.kmask, scalars recomputed from the rows
 //   CSRM (with REC = false): the mask is in CSR order (node-centric mode): bit of csc_eid[q]
-template <int VEC, int G, int R, bool REC, bool CSRM>
+template <int VEC, int G, int R, bool REC, bool CSRM, typename S = float>
 __device__ __forceinline__ void s_role_small(const BwdArgs &a, int blk, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -394,7 +400,7 @@ __device__ __forceinline__ void s_role_small(const BwdArgs &a, int blk, int *lds
     if (slot >= a.s_small_end) return;
     const int4 d = a.sdesc[slot];
     const int v = d.x, qs = d.y, od = d.z;
-    FinishRows<VEC, G, R> fin;
+    FinishRows<VEC, G, R, S> fin;
     fin.load(a, v, lg);
     int *s_i = lds_wave + gid * 3 * SMALL_T;                          // kept out-edges: target row
     float *s_w = reinterpret_cast<float *>(s_i + SMALL_T);
@@ -434,10 +440,10 @@ __device__ __forceinline__ void s_role_small(const BwdArgs &a, int blk, int *lds
         const int q1 = two ? q0 + 1 : q0;
         const int i0 = s_i[q0], i1 = s_i[q1];
         RowT x0, g0, x1, g1;
-        x0.load(a.h + (size_t)(i0 + a.row_off) * a.C, a.C, lg);
-        g0.load(a.gout + (size_t)i0 * a.C, a.C, lg);
-        x1.load(a.h + (size_t)(i1 + a.row_off) * a.C, a.C, lg);
-        g1.load(a.gout + (size_t)i1 * a.C, a.C, lg);
+        x0.load(a.hrows<S>() + (size_t)(i0 + a.row_off) * a.C, a.C, lg);
+        g0.load(a.grows<S>() + (size_t)i0 * a.C, a.C, lg);
+        x1.load(a.hrows<S>() + (size_t)(i1 + a.row_off) * a.C, a.C, lg);
+        g1.load(a.grows<S>() + (size_t)i1 * a.C, a.C, lg);
         // (odd count: the repeat enters with zero weights - unconditional, so that all four row
         // loads are in flight together)
         if constexpr (REC) {
@@ -458,7 +464,7 @@ __device__ __forceinline__ void s_role_small(const BwdArgs &a, int blk, int *lds
             s_edge_recompute<VEC, G, R>(x1, g1, fin.hv, invv, d1, two ? 1.0f : 0.0f, msg, dns);
         }
     }
-    s_finish<VEC, G, R>(a, v, lg, msg, dns, fin);
+    s_finish<VEC, G, R, S>(a, v, lg, msg, dns, fin);
 }
 
 // ------------------------- node-centric work item ---------------------------
@@ -472,7 +478,7 @@ __device__ __forceinline__ void s_role_small(const BwdArgs &a, int blk, int *lds
 // ascending, T then S), so the result equals theirs bit for bit.
 // The kept bits come from k_pack_kept's mask in CSR order (below): in-edges by position, out-edges
 // through csc_eid.
-template <int VEC, int G, int R, bool KB = false>
+template <int VEC, int G, int R, bool KB = false, typename S = float>
 __device__ __forceinline__ void f_role_node(const BwdArgs &a, int blk, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -486,10 +492,10 @@ __device__ __forceinline__ void f_role_node(const BwdArgs &a, int blk, int *lds_
     const int vl = v - a.row_off;
     int *s_j = lds_wave + gid * 2 * SMALL_T;     // kept in-edges: source id
     int *s_i = s_j + SMALL_T;                    // kept out-edges: target row
-    FinishRows<VEC, G, R> fin;                   // .t becomes dnT_v, .hv = h_v (raw)
+    FinishRows<VEC, G, R, S> fin;                   // .t becomes dnT_v, .hv = h_v (raw)
     RowT gp;
-    gp.load(a.gout + (size_t)vl * a.C, a.C, lg);
-    fin.hv.load(a.h + (size_t)v * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)vl * a.C, a.C, lg);
+    fin.hv.load(a.hrows<S>() + (size_t)v * a.C, a.C, lg);
     fin.own = true;
     int nk = 0, nko = 0;
     unsigned hw = 0u;                                        // KB: the row's own 16 kept bits, one 2-byte load
@@ -536,9 +542,9 @@ __device__ __forceinline__ void f_role_node(const BwdArgs &a, int blk, int *lds_
             to[u] = q < nko;
             const int j = ti[u] ? s_j[q] : v;
             const int i = to[u] ? s_i[q] : vl;
-            xj[u].load(a.h + (size_t)j * a.C, a.C, lg);
-            x[u].load(a.h + (size_t)(i + a.row_off) * a.C, a.C, lg);
-            gi[u].load(a.gout + (size_t)i * a.C, a.C, lg);
+            xj[u].load(a.hrows<S>() + (size_t)j * a.C, a.C, lg);
+            x[u].load(a.hrows<S>() + (size_t)(i + a.row_off) * a.C, a.C, lg);
+            gi[u].load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
             dd[u] = a.inv_deg[i];                                        // travels with the rows
         }
 #pragma unroll
@@ -547,7 +553,7 @@ __device__ __forceinline__ void f_role_node(const BwdArgs &a, int blk, int *lds_
         for (int u = 0; u < FU; ++u)
             s_edge_recompute<VEC, G, R>(x[u], gi[u], fin.hv, invv, dd[u], to[u] ? 1.0f : 0.0f, msg, dns);
     }
-    s_finish<VEC, G, R>(a, v, lg, msg, dns, fin);
+    s_finish<VEC, G, R, S>(a, v, lg, msg, dns, fin);
 }
 
 // inclusive prefix sum over the lanes of a wave
@@ -572,7 +578,7 @@ __device__ __forceinline__ int wave_prefix_incl(int v)
 // so pass S has nothing left but split sources and, under a partition, the halo's sources.
 // Robust against a wrong hint: a list that would overflow is flushed (gathered and
 // accumulated) first - slower, still correct and deterministic.
-template <int VEC, int G, int R, bool KB = false>
+template <int VEC, int G, int R, bool KB = false, typename S = float>
 __device__ __forceinline__ void w_role_node(const BwdArgs &a, int blk, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -585,10 +591,10 @@ __device__ __forceinline__ void w_role_node(const BwdArgs &a, int blk, int *lds_
     const int vl = d.x, rs = d.y, deg = d.z;
     const int v = vl + a.row_off;
     const int qs = a.cscptr[v], od = a.cscptr[v + 1] - qs;
-    FinishRows<VEC, G, R> fin;                   // .t becomes dnT_v
+    FinishRows<VEC, G, R, S> fin;                   // .t becomes dnT_v
     RowT gp;
-    gp.load(a.gout + (size_t)vl * a.C, a.C, lg);
-    fin.hv.load(a.h + (size_t)v * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)vl * a.C, a.C, lg);
+    fin.hv.load(a.hrows<S>() + (size_t)v * a.C, a.C, lg);
     fin.own = true;
     gp.scale(1.0f / (float)max(deg, 1));
     fin.t.zero();
@@ -606,8 +612,8 @@ __device__ __forceinline__ void w_role_node(const BwdArgs &a, int blk, int *lds_
         for (int q0 = 0; q0 < n; q0 += 2 * NG) {
             const int qa = min(q0 + gid, n - 1), qb = min(q0 + NG + gid, n - 1);
             RowT xa, xb;
-            xa.load(a.h + (size_t)elist[qa] * a.C, a.C, lg);
-            xb.load(a.h + (size_t)elist[qb] * a.C, a.C, lg);
+            xa.load(a.hrows<S>() + (size_t)elist[qa] * a.C, a.C, lg);
+            xb.load(a.hrows<S>() + (size_t)elist[qb] * a.C, a.C, lg);
             t_edge_row<VEC, G, R>(xa, gp, fin.t, q0 + gid < n ? 1.0f : 0.0f);
             t_edge_row<VEC, G, R>(xb, gp, fin.t, q0 + NG + gid < n ? 1.0f : 0.0f);
         }
@@ -701,17 +707,17 @@ __device__ __forceinline__ void w_role_node(const BwdArgs &a, int blk, int *lds_
         const bool la = q0 + gid < nso, lb = q0 + NG + gid < nso;
         const int ia = s_i[qa], ib = s_i[qb];
         RowT xa, ga, xb, gb;
-        xa.load(a.h + (size_t)(ia + a.row_off) * a.C, a.C, lg);
-        ga.load(a.gout + (size_t)ia * a.C, a.C, lg);
-        xb.load(a.h + (size_t)(ib + a.row_off) * a.C, a.C, lg);
-        gb.load(a.gout + (size_t)ib * a.C, a.C, lg);
+        xa.load(a.hrows<S>() + (size_t)(ia + a.row_off) * a.C, a.C, lg);
+        ga.load(a.grows<S>() + (size_t)ia * a.C, a.C, lg);
+        xb.load(a.hrows<S>() + (size_t)(ib + a.row_off) * a.C, a.C, lg);
+        gb.load(a.grows<S>() + (size_t)ib * a.C, a.C, lg);
         const float da = a.inv_deg[ia], db = a.inv_deg[ib];
         s_edge_recompute<VEC, G, R>(xa, ga, fin.hv, invv, da, la ? 1.0f : 0.0f, msg, dns);
         s_edge_recompute<VEC, G, R>(xb, gb, fin.hv, invv, db, lb ? 1.0f : 0.0f, msg, dns);
     }
     msg.reduce_across_groups();
     dns.reduce_across_groups();
-    if (gid == 0) s_finish<VEC, G, R>(a, v, lg, msg, dns, fin);
+    if (gid == 0) s_finish<VEC, G, R, S>(a, v, lg, msg, dns, fin);
 }
 
 // kept bits of the forward's per-edge weights, in CSR (edge) order: one pass over wsel, whole
@@ -743,7 +749,7 @@ static __global__ __launch_bounds__(256) void k_pack_kept(const float *__restric
 #define SNGNN_BWDF_ATTR __attribute__((amdgpu_waves_per_eu(R == 1 ? 8 : 1, 8)))
 // selective calls: every owned node in one launch - a wave per node that is not fused (heavy rows
 // first), then the fused nodes
-template <int VEC, int G, int R, bool KB = false>
+template <int VEC, int G, int R, bool KB = false, typename S = float>
 __global__ __launch_bounds__(BLOCK) SNGNN_BWDF_ATTR void k_bwd_w(const BwdArgs a)
 {
     __shared__ __align__(16) int lds[WAVES][2 * WAVE_T];
@@ -755,25 +761,25 @@ __global__ __launch_bounds__(BLOCK) SNGNN_BWDF_ATTR void k_bwd_w(const BwdArgs a
     // memory system (62 -> 5x us).
     const int stride = a.nbB;
     const int cw = min(a.nbA, (b + stride - 1) / stride);          // wave-per-node workgroups before b
-    if (b % stride == 0 && b / stride < a.nbA) { if (a.role_mask & 1) w_role_node<VEC, G, R, KB>(a, b / stride, lw); }
-    else if (a.role_mask & 2) f_role_node<VEC, G, R, KB>(a, b - cw, lw);
+    if (b % stride == 0 && b / stride < a.nbA) { if (a.role_mask & 1) w_role_node<VEC, G, R, KB, S>(a, b / stride, lw); }
+    else if (a.role_mask & 2) f_role_node<VEC, G, R, KB, S>(a, b - cw, lw);
 }
 
 // pass T of the targets that are not fused (split-row tasks, wave rows, small targets with a
 // long out-list) and the fused nodes, in one launch
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) SNGNN_BWDF_ATTR void k_bwd_f(const BwdArgs a)
 {
     __shared__ __align__(16) int lds[WAVES][256];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
-    if (b < a.nbA) t_role_wave<VEC, G, R, false>(a, b, lw, true);
-    else if (b < a.nbA + a.nbB) t_role_wave<VEC, G, R, false>(a, b - a.nbA, lw, false);
-    else if (b < a.nbA + a.nbB + a.nbC) t_role_small<VEC, G, R, false>(a, b - a.nbA - a.nbB, lw, a.trest, a.n_trest);
-    else f_role_node<VEC, G, R>(a, b - a.nbA - a.nbB - a.nbC, lw);
+    if (b < a.nbA) t_role_wave<VEC, G, R, false, S>(a, b, lw, true);
+    else if (b < a.nbA + a.nbB) t_role_wave<VEC, G, R, false, S>(a, b - a.nbA, lw, false);
+    else if (b < a.nbA + a.nbB + a.nbC) t_role_small<VEC, G, R, false, S>(a, b - a.nbA - a.nbB, lw, a.trest, a.n_trest);
+    else f_role_node<VEC, G, R, false, S>(a, b - a.nbA - a.nbB - a.nbC, lw);
 }
 
-template <int VEC, int G, int R, bool REC, bool CSRM>
+template <int VEC, int G, int R, bool REC, bool CSRM, typename S = float>
 __device__ __forceinline__ void s_role_wave(const BwdArgs &a, int blk, int *lds_wave, bool task)
 {
     using RowT = Row<VEC, G, R>;
@@ -798,7 +804,7 @@ __device__ __forceinline__ void s_role_wave(const BwdArgs &a, int blk, int *lds_
     const int e1 = task ? min(od, e0 + CHUNK) : od;
     RowT hv;                                                      // own row (raw): every group its copy
     float invv = 0.f;
-    if constexpr (!REC) hv.load(a.h + (size_t)v * a.C, a.C, lg);
+    if constexpr (!REC) hv.load(a.hrows<S>() + (size_t)v * a.C, a.C, lg);
     int *s_i = lds_wave;                                         // [WAVE_T] kept target rows
     float2 *s_rec = reinterpret_cast<float2 *>(lds_wave + WAVE_T);   // their records
     int nsel = 0;
@@ -836,10 +842,10 @@ __device__ __forceinline__ void s_role_wave(const BwdArgs &a, int blk, int *lds_
         const bool la = q0 + gid < nsel, lb = q0 + NG + gid < nsel;
         const int ia = s_i[qa], ib = s_i[qb];
         RowT xa, ga, xb, gb;
-        xa.load(a.h + (size_t)(ia + a.row_off) * a.C, a.C, lg);
-        ga.load(a.gout + (size_t)ia * a.C, a.C, lg);
-        xb.load(a.h + (size_t)(ib + a.row_off) * a.C, a.C, lg);
-        gb.load(a.gout + (size_t)ib * a.C, a.C, lg);
+        xa.load(a.hrows<S>() + (size_t)(ia + a.row_off) * a.C, a.C, lg);
+        ga.load(a.grows<S>() + (size_t)ia * a.C, a.C, lg);
+        xb.load(a.hrows<S>() + (size_t)(ib + a.row_off) * a.C, a.C, lg);
+        gb.load(a.grows<S>() + (size_t)ib * a.C, a.C, lg);
         if constexpr (REC) {
             float2 ra = s_rec[qa], rb = s_rec[qb];
             if (a.rec_dot) {                                      // (uniform) raw records: BwdArgs::rec_dot
@@ -867,25 +873,25 @@ __device__ __forceinline__ void s_role_wave(const BwdArgs &a, int blk, int *lds_
             dns.store(a.partS + (size_t)tq * 2 * a.C + a.C, a.C, lg);
         }
     } else if (gid == 0) {
-        FinishRows<VEC, G, R> fin;
+        FinishRows<VEC, G, R, S> fin;
         fin.load(a, v, lg);
-        s_finish<VEC, G, R>(a, v, lg, msg, dns, fin);
+        s_finish<VEC, G, R, S>(a, v, lg, msg, dns, fin);
     }
 }
 
-template <int VEC, int G, int R, bool REC, bool CSRM = false>
+template <int VEC, int G, int R, bool REC, bool CSRM = false, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_bwd_s(const BwdArgs a)
 {
     __shared__ __align__(16) int lds[WAVES][512];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
-    if (b < a.nbA) s_role_wave<VEC, G, R, REC, CSRM>(a, b, lw, true);
-    else if (b < a.nbA + a.nbB) s_role_wave<VEC, G, R, REC, CSRM>(a, b - a.nbA, lw, false);
-    else s_role_small<VEC, G, R, REC, CSRM>(a, b - a.nbA - a.nbB, lw);
+    if (b < a.nbA) s_role_wave<VEC, G, R, REC, CSRM, S>(a, b, lw, true);
+    else if (b < a.nbA + a.nbB) s_role_wave<VEC, G, R, REC, CSRM, S>(a, b - a.nbA, lw, false);
+    else s_role_small<VEC, G, R, REC, CSRM, S>(a, b - a.nbA - a.nbB, lw);
 }
 
 // split sources: one wave per source sums the tasks' partial rows, then finishes
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(64) void k_bwd_s_fin(const BwdArgs a)
 {
     using RowT = Row<VEC, G, R>;
@@ -904,9 +910,9 @@ __global__ __launch_bounds__(64) void k_bwd_s_fin(const BwdArgs a)
         t.load(a.partS + (size_t)tq * 2 * a.C + a.C, a.C, lg);
         dns.add(t);
     }
-    FinishRows<VEC, G, R> fin;
+    FinishRows<VEC, G, R, S> fin;
     fin.load(a, v, lg);
-    s_finish<VEC, G, R>(a, v, lg, msg, dns, fin);
+    s_finish<VEC, G, R, S>(a, v, lg, msg, dns, fin);
 }
 
 static __global__ void k_clear_words(unsigned *__restrict__ p, int64_t n)
@@ -914,7 +920,7 @@ static __global__ void k_clear_words(unsigned *__restrict__ p, int64_t n)
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0u;
 }
 
-template <int VEC, int G, int R> int launch_agg_bwd(const BwdArgs &a0, hipStream_t st)
+template <int VEC, int G, int R, typename S = float> int launch_agg_bwd(const BwdArgs &a0, hipStream_t st)
 {
     constexpr int RPW = 64 / G;
     BwdArgs a = a0;
@@ -933,14 +939,14 @@ template <int VEC, int G, int R> int launch_agg_bwd(const BwdArgs &a0, hipStream
             const int nbF = ceil_div(a.n_fused, (int64_t)WAVES * RPW);
             a.nbB = std::max(1, (a.nbA + nbF) / std::max(a.nbA, 1));          // k_bwd_w: spacing of the wave-per-node workgroups
             if (a.nbA + nbF > 0) {
-                if (a.kbits) k_bwd_w<VEC, G, R, true><<<a.nbA + nbF, BLOCK, 0, st>>>(a);
-                else k_bwd_w<VEC, G, R, false><<<a.nbA + nbF, BLOCK, 0, st>>>(a);
+                if (a.kbits) k_bwd_w<VEC, G, R, true, S><<<a.nbA + nbF, BLOCK, 0, st>>>(a);
+                else k_bwd_w<VEC, G, R, false, S><<<a.nbA + nbF, BLOCK, 0, st>>>(a);
             }
             if (a.n_stasks > 0) {
                 a.nbA = ceil_div(a.n_stasks, WAVES);
                 a.nbB = 0;
-                k_bwd_s<VEC, G, R, false, true><<<a.nbA, BLOCK, 0, st>>>(a);
-                k_bwd_s_fin<VEC, G, R><<<a.n_ssplit, 64, 0, st>>>(a);
+                k_bwd_s<VEC, G, R, false, true, S><<<a.nbA, BLOCK, 0, st>>>(a);
+                k_bwd_s_fin<VEC, G, R, S><<<a.n_ssplit, 64, 0, st>>>(a);
             }
             SN_HIP(hipGetLastError());
             return SNGNN_OK;
@@ -950,13 +956,13 @@ template <int VEC, int G, int R> int launch_agg_bwd(const BwdArgs &a0, hipStream
         a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
         a.nbC = ceil_div(a.n_trest, (int64_t)WAVES * RPW);
         const int nbD = ceil_div(a.n_fused, (int64_t)WAVES * RPW);
-        if (a.nbA + a.nbB + a.nbC + nbD > 0) k_bwd_f<VEC, G, R><<<a.nbA + a.nbB + a.nbC + nbD, BLOCK, 0, st>>>(a);
+        if (a.nbA + a.nbB + a.nbC + nbD > 0) k_bwd_f<VEC, G, R, S><<<a.nbA + a.nbB + a.nbC + nbD, BLOCK, 0, st>>>(a);
         if (a.n_split > 0) k_bwd_t_fin<<<a.n_split, 256, 0, st>>>(a);
         a.nbA = ceil_div(a.n_stasks, WAVES);
         a.nbB = ceil_div(a.n_smed_end - a.n_ssplit, WAVES);
         const int nbS = ceil_div(a.s_small_end - a.n_smed_end, (int64_t)WAVES * RPW);
-        if (a.nbA + a.nbB + nbS > 0) k_bwd_s<VEC, G, R, false, true><<<a.nbA + a.nbB + nbS, BLOCK, 0, st>>>(a);
-        if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R><<<a.n_ssplit, 64, 0, st>>>(a);
+        if (a.nbA + a.nbB + nbS > 0) k_bwd_s<VEC, G, R, false, true, S><<<a.nbA + a.nbB + nbS, BLOCK, 0, st>>>(a);
+        if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R, S><<<a.n_ssplit, 64, 0, st>>>(a);
         SN_HIP(hipGetLastError());
         return SNGNN_OK;
     }
@@ -970,14 +976,14 @@ template <int VEC, int G, int R> int launch_agg_bwd(const BwdArgs &a0, hipStream
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
     int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_bwd_t<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_bwd_t<VEC, G, R, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_bwd_t_fin<<<a.n_split, 256, 0, st>>>(a);
     // pass S (sources)
     a.nbA = ceil_div(a.n_stasks, WAVES);
     a.nbB = ceil_div(a.n_smed_end - a.n_ssplit, WAVES);
     nbC = ceil_div(a.s_small_end - a.n_smed_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, false><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R><<<a.n_ssplit, 64, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, false, false, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R, S><<<a.n_ssplit, 64, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -985,5 +991,19 @@ template <int VEC, int G, int R> int launch_agg_bwd(const BwdArgs &a0, hipStream
 int launch_agg_bwd_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 int launch_agg_bwd_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 int launch_agg_bwd_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+// the half path (sngnn_agg_backward_half: h, gout and grad_h stored as S), one translation unit per storage type
+// and VEC (agg_bwd_f16_v*.hip, agg_bwd_bf16_v*.hip)
+template <typename S> struct LaunchBwdHalf {
+    template <int VEC, int G, int R> static int run(const BwdArgs &a, hipStream_t st)
+    {
+        return launch_agg_bwd<VEC, G, R, S>(a, st);
+    }
+};
+int launch_agg_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_agg_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_agg_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_agg_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_agg_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_agg_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 
 }  // namespace sngnn

@@ -174,7 +174,8 @@ extern "C" int sngnn_filter_pair_scores(const void *filt, int C, const int64_t *
 static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const float *n, const float *nrm,
                               const void *filt, int C, int top_k, float thr, float *out, float *wsel, float *inv_norm,
                               int32_t *sel_src, float *sel_w, void *scratch, hipEvent_t *ev, hipStream_t st,
-                              const uint8_t *row_flag = nullptr, int row_want = 0, const sngnn_epilogue_t *epi = nullptr)
+                              const uint8_t *row_flag = nullptr, int row_want = 0, const sngnn_epilogue_t *epi = nullptr,
+                              int dtype = 0)
 {
     if (top_k > (1 << 20)) top_k = 1 << 20;     // more than any row can use
 
@@ -272,6 +273,15 @@ static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const f
                                   : (top_k < 0 ? g->rows_gt((int64_t)16 * CHUNK) : 0);
     a.lowbits = 1;
     while ((1ll << a.lowbits) < g->max_in_deg && a.lowbits < 31) ++a.lowbits;
+    if (dtype != 0) {
+        // the half path (sngnn_agg_forward_half: n = the raw half rows, nrm == NULL, no epilogue / head / kept bits)
+        const bool f16 = dtype == SNGNN_DTYPE_F16;
+        switch (cfg.vec) {
+        case 1: return f16 ? launch_agg_fwd_f16_v1(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v1(cfg, a, max_split, ev, st);
+        case 2: return f16 ? launch_agg_fwd_f16_v2(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v2(cfg, a, max_split, ev, st);
+        default: return f16 ? launch_agg_fwd_f16_v4(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v4(cfg, a, max_split, ev, st);
+        }
+    }
     if (head) {
         SN_REQUIRE(g->n_split == 0 || a.use_cand, SNGNN_EINVAL,
                    "no head epilogue: this graph's biggest row takes the scratch-score finalize (sngnn_agg_head_supported)");
@@ -376,6 +386,32 @@ extern "C" int sngnn_agg_forward(const sngnn_graph_t *g, const float *h, int C, 
                                  int32_t *sel_src, float *sel_w, void *workspace, void *stream)
 {
     return agg_forward_impl(g, h, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w, workspace, stream, nullptr);
+}
+
+// The half path: h and out stored as fp16 / bf16, always scored on the fly (knob 2 = 2's form: the table path would
+// need a unit-row table of the half rows' fp32 values - a pass, and 4 C bytes per row where the rows have 2 C).
+extern "C" int sngnn_agg_forward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, int top_k, float thr,
+                                      void *out, float *wsel, float *inv_norm, int32_t *sel_src, float *sel_w,
+                                      void *workspace, void *stream)
+{
+    SN_REQUIRE(dtype == SNGNN_DTYPE_F16 || dtype == SNGNN_DTYPE_BF16, SNGNN_EINVAL,
+               "dtype must be SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16");
+    SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
+    SN_REQUIRE(g->N == 0 || (h != nullptr && out != nullptr), SNGNN_EINVAL, "h/out is NULL");
+    RowCfg cfg;
+    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL, "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
+    SN_REQUIRE(((uintptr_t)h % (cfg.vec * 2)) == 0 && ((uintptr_t)out % (cfg.vec * 2)) == 0, SNGNN_EINVAL,
+               "h/out must be aligned to the row vector width (2 * vec bytes)");
+    SN_REQUIRE((sel_src == nullptr) == (sel_w == nullptr), SNGNN_EINVAL, "sel_src and sel_w go together");
+    SN_REQUIRE(sel_src == nullptr || top_k >= 0, SNGNN_EINVAL, "sel_src needs top_k >= 0");
+    if (g->N == 0) return SNGNN_OK;
+    SN_REQUIRE(workspace != nullptr, SNGNN_EINVAL, "workspace is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t *ev = g_prof_on ? g_prof_ev : nullptr;
+    if (ev) SN_HIP(hipEventRecord(ev[0], st));
+    return forward_normalized(g, cfg, (const float *)h, nullptr, nullptr, C, top_k, thr, (float *)out, wsel, inv_norm,
+                              sel_src, sel_w, (char *)workspace + fwd_table_bytes(g->Ntot, C), ev ? ev + 1 : nullptr, st,
+                              nullptr, 0, nullptr, dtype);
 }
 
 extern "C" int64_t sngnn_agg_head_workspace_bytes(const sngnn_graph_t *g)

@@ -51,6 +51,8 @@ struct FwdArgs {
     // of another edge whose rank is asked for - the edge is scored again exactly (IEEE
     // normalisation of the two rows in registers, the table path's dot), so selections, ties
     // included, are those of the table path, bit for bit, without the normalisation pass.
+    // (the half path, sngnn_agg_forward_half: n holds __half / __hip_bfloat16 rows and out is stored in that type -
+    // the kernels' template parameter S; rows<S>() / outs<S>() / out_at<S>() below.  Everything else stays fp32.)
     const float *n;
     const float *nrm;
     float delta;          // OTF: bound on |fast - exact| (launcher: (4 C + 32) 2^-24)
@@ -97,6 +99,15 @@ struct FwdArgs {
     const uint8_t *row_flag;
     int row_want;
     __device__ __forceinline__ bool skip_row(int i) const { return row_flag != nullptr && row_flag[i] != row_want; }
+    // n and out in their storage type S (float: the pointers themselves)
+    template <typename S> __device__ __forceinline__ const S *rows() const { return reinterpret_cast<const S *>(n); }
+    template <typename S> __device__ __forceinline__ S *outs() const { return reinterpret_cast<S *>(out); }
+    // one value of out: `a.out_at<S>(idx) = v` (float: the plain element itself)
+    template <typename S> __device__ __forceinline__ decltype(auto) out_at(size_t idx) const
+    {
+        if constexpr (std::is_same<S, float>::value) return (out[idx]);
+        else return HalfRef<S>{outs<S>() + idx};
+    }
     // store epilogue of a hidden layer (models.py:204-209: conv -> [+ bias] -> relu_ -> dropout), applied to
     // the finished mean row on its way out: out = keep ? max(mean + bias, 0) * scale : 0.
     // epi_flags: bit 0 relu, bit 1 bias, bit 2 keep mask; 0 = none (sngnn_agg_forward_epilogue).
@@ -517,7 +528,7 @@ __device__ __forceinline__ WaveSel wave_select(const float *sc, int n, int base,
 // ---------------------------------------------------------------------------
 // One set of 64/G small rows (one per lane group) whose column ids are already in
 // LDS (s_col[gid][t]).  d = this group's row descriptor (deg 0 for a padding slot).
-template <int VEC, int G, int R, bool OTF, int EPI>
+template <int VEC, int G, int R, bool OTF, int EPI, typename S = float>
 __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, bool valid,
                                                int *lds_wave, const int *s_col_set)
 {
@@ -537,7 +548,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
     float *s_w = reinterpret_cast<float *>(lds_wave + 3 * SETW) + gid * SMALL_T;
 
     RowT ni;
-    ni.load(a.n + (size_t)self * a.C, a.C, lg);
+    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
     const int dmax = wave_max_i(deg);
     float inv_i = 0.f, q_i = 0.f;
     if constexpr (OTF) {
@@ -554,7 +565,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = (t0 + u) < deg ? s_col[t0 + u] : self;
-            x[u].load(a.n + (size_t)j * a.C, a.C, lg);
+            x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
             if constexpr (OTF) nj[u] = 1.f;
             else nj[u] = rank ? 0.f : a.nrm[j];   // a streaming row weighs the row it has just scored
         }
@@ -619,7 +630,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
                 for (int t = 0; t < dm; ++t) {
                     const bool live = row_amb && t < deg;
                     RowT xr;
-                    xr.load(a.n + (size_t)(live ? s_col[t] : self) * a.C, a.C, lg);
+                    xr.load(a.rows<S>() + (size_t)(live ? s_col[t] : self) * a.C, a.C, lg);
                     const float se = exact_score_raw<VEC, G, R>(nu, xr);
                     if (live && lg == 0) s_sc[t] = se;
                 }
@@ -657,7 +668,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
                 if (w != SNGNN_UNSELECTED) {
                     const int j = s_col[t];
                     RowT xr;
-                    xr.load(a.n + (size_t)j * a.C, a.C, lg);
+                    xr.load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
                     if constexpr (OTF) acc.axpy(w, xr);
                     else acc.axpy(w * a.nrm[j], xr);
                 }
@@ -670,7 +681,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
     if (valid) {
         acc.div((float)max(deg, 1));
         if constexpr (EPI == 1) row_epilogue<VEC, G, R>(a, acc, i, lg);
-        acc.store(a.out + (size_t)i * a.C, a.C, lg);
+        acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     }
 }
 
@@ -842,7 +853,7 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
 // current one, so a set costs one memory round trip (its feature rows) instead of a
 // chain of three (descriptor -> columns -> rows).
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool OTF, int EPI, bool FS = false>
+template <int VEC, int G, int R, bool OTF, int EPI, bool FS = false, typename S = float>
 __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int stride, int nsets, int *lds_wave)
 {
     constexpr int RPW = 64 / G;
@@ -902,7 +913,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
                     done = true;
                 }
             }
-            if (!done) small_rows_set<VEC, G, R, OTF, EPI>(a, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
+            if (!done) small_rows_set<VEC, G, R, OTF, EPI, S>(a, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
         }
         store_cols(cols, lds_wave + SETW * (buf ^ 1));
         d_cur = d_nxt;
@@ -927,7 +938,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
 //           except: a streaming edge within delta of thr is scored exactly; with exact_all EVERY
 //           edge is (the paths that rank from scores in HBM scratch: top_k > CAND_MAX_K, hubs
 //           beyond the candidate finalize, ranks of a streaming split row).
-template <int VEC, int G, int R, bool OTF>
+template <int VEC, int G, int R, bool OTF, typename S = float>
 __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, int e0, int e1,
                                             const Row<VEC, G, R> &ni, float inv_i, bool stream,
                                             float *sc, int sc_off, Row<VEC, G, R> &acc,
@@ -963,7 +974,7 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, 
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            x[u].load(a.n + (size_t)j[u] * a.C, a.C, lg);
+            x[u].load(a.rows<S>() + (size_t)j[u] * a.C, a.C, lg);
             if constexpr (OTF) nj[u] = 1.f;
             else nj[u] = stream ? a.nrm[j[u]] : 0.f;
         }
@@ -1010,7 +1021,7 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, 
 // sc[idx] = <n_i, n_j>.  U rows per lane group in flight; a slot past the end repeats the
 // last listed edge and stores nothing.
 // (OTF: ni is the UNIT target row, the listed rows are raw and are normalised in registers)
-template <int VEC, int G, int R, bool OTF>
+template <int VEC, int G, int R, bool OTF, typename S = float>
 __device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R> &ni, const int *list, int ncand,
                                            const int *ids, float *sc)
 {
@@ -1029,7 +1040,7 @@ __device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R
         for (int u = 0; u < U; ++u) {
             const int q = q0 + u * NG + gid;
             idx[u] = list[min(q, ncand - 1)];
-            x[u].load(a.n + (size_t)ids[idx[u]] * a.C, a.C, lg);
+            x[u].load(a.rows<S>() + (size_t)ids[idx[u]] * a.C, a.C, lg);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -1058,7 +1069,7 @@ __device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R
 //         ones).  Only a row that fails this test - ties and near ties at the cut - takes the
 //         candidate path.  (Not for split-row tasks: their keys are merged with other tasks'
 //         keys by the finalize, which needs them exact; not when ranks are emitted.)
-template <int VEC, int G, int R, bool OTF>
+template <int VEC, int G, int R, bool OTF, typename S = float>
 __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC, G, R> &ni, float inv_i, int self,
                                                  int rs, int e0, int e1, float *sc, int *list, int *ids, int lowbits,
                                                  bool optimistic = false)
@@ -1070,7 +1081,7 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
     if constexpr (OTF) {
         RowT unused;
         unused.zero();
-        score_edges<VEC, G, R, true>(a, self, rs, e0, e1, ni, inv_i, false, sc, e0, unused, ids);
+        score_edges<VEC, G, R, true, S>(a, self, rs, e0, e1, ni, inv_i, false, sc, e0, unused, ids);
         eps = a.delta;
     } else {
         constexpr int GF = G * R / 2;                // 16-byte lanes per filter row (VEC == 4)
@@ -1110,7 +1121,7 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
         if constexpr (OTF) {
             RowT nu = ni;
             normalize_in_place<VEC, G, R>(nu);
-            score_list<VEC, G, R, true>(a, nu, list, ncand, ids, sc);
+            score_list<VEC, G, R, true, S>(a, nu, list, ncand, ids, sc);
         } else {
             score_list<VEC, G, R, false>(a, ni, list, ncand, ids, sc);
         }
@@ -1127,7 +1138,7 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
 // ---------------------------------------------------------------------------
 // Class B: SMALL_T < deg <= WAVE_T, one wave per row.
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool FILT, bool OTF, int EPI>
+template <int VEC, int G, int R, bool FILT, bool OTF, int EPI, typename S = float>
 __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -1148,7 +1159,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     int *s_ids = lds_wave + 2 * WAVE_T;                      // [WAVE_T]
 
     RowT ni;
-    ni.load(a.n + (size_t)self * a.C, a.C, lg);
+    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
     float inv_i = 0.f, q_i = 0.f;
     if constexpr (OTF) {
         q_i = group_sum<G>(ni.dot_partial(ni));
@@ -1161,14 +1172,14 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     // asked for on a streaming row included: their order needs exact scores too)
     const bool banded = OTF ? need_sc : (FILT && rank && deg >= a.filt_min_deg);
     if (!banded)
-        score_edges<VEC, G, R, OTF>(a, self, rs, 0, deg, ni, inv_i, !rank, need_sc ? s_sc : nullptr, 0, acc,
+        score_edges<VEC, G, R, OTF, S>(a, self, rs, 0, deg, ni, inv_i, !rank, need_sc ? s_sc : nullptr, 0, acc,
                                     rank ? s_ids : nullptr);
 
     if (need_sc) {
         WaveSel ws;
         if constexpr (FILT || OTF) {
             if (banded) {
-                ws = banded_select<VEC, G, R, OTF>(a, ni, inv_i, self, rs, 0, deg, s_sc, s_list, s_ids, 7,
+                ws = banded_select<VEC, G, R, OTF, S>(a, ni, inv_i, self, rs, 0, deg, s_sc, s_list, s_ids, 7,
                                                    /*optimistic=*/OTF && !emit);
             } else {
                 wave_lds_sync();
@@ -1219,7 +1230,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
                     const int idx = s_list[min(q, nsel - 1)];
                     const int j = s_ids[idx];
                     w[u] = q < nsel ? s_sc[idx] : 0.f;
-                    x[u].load(a.n + (size_t)j * a.C, a.C, lg);
+                    x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
                     if constexpr (OTF) nj[u] = 1.f;
                     else nj[u] = a.nrm[j];
                 }
@@ -1232,7 +1243,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     if (gid == 0) {
         acc.div((float)deg);
         if constexpr (EPI == 1) row_epilogue<VEC, G, R>(a, acc, i, lg);
-        acc.store(a.out + (size_t)i * a.C, a.C, lg);
+        acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     }
     // (stored at the END of the row: a store up front would pin the scoring pass's first
     // column-id loads behind it - the pointers are not restrict)
@@ -1249,7 +1260,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
 // FIN: the row's finalize runs in THIS launch (fin_block_pair / fin_group_batch / fin_stream_row) - what it reads
 // or overwrites is stored at agent scope, then the task says "done".  The launches whose finalize is the next
 // launch run the FIN = false instantiation: plain stores, the code of round 4.
-template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN>
+template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN, typename S = float>
 __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -1266,7 +1277,7 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wav
     const bool cand = rank && a.use_cand;        // chunk-local top-k -> candidates
 
     RowT ni;
-    ni.load(a.n + (size_t)self * a.C, a.C, lg);
+    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
     float inv_i = 0.f;
     if constexpr (OTF) {
         const float q_i = group_sum<G>(ni.dot_partial(ni));
@@ -1281,14 +1292,14 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wav
     float *s_sc = reinterpret_cast<float *>(lds_wave);          // [CHUNK], chunk-local
     float *sc_glb = (!cand && (rank || emit)) ? a.scores + a.split_soff[p] : nullptr;   // HBM scratch
     if ((FILT || OTF) && cand) { /* scored below, in two precisions */ }
-    else if (cand) score_edges<VEC, G, R, OTF>(a, self, rs, e0, e1, ni, inv_i, !rank, s_sc, e0, acc);   // LDS
+    else if (cand) score_edges<VEC, G, R, OTF, S>(a, self, rs, e0, e1, ni, inv_i, !rank, s_sc, e0, acc);   // LDS
     // HBM scratch (ranked later from those scores: OTF writes exact ones) / none (pure streaming)
-    else score_edges<VEC, G, R, OTF>(a, self, rs, e0, e1, ni, inv_i, !rank, sc_glb, 0, acc, nullptr,
+    else score_edges<VEC, G, R, OTF, S>(a, self, rs, e0, e1, ni, inv_i, !rank, sc_glb, 0, acc, nullptr,
                                      /*exact_all=*/sc_glb != nullptr);
     if (cand) {
         WaveSel ws;
         if constexpr (FILT || OTF) {
-            ws = banded_select<VEC, G, R, OTF>(a, ni, inv_i, self, rs, e0, e1, s_sc, lds_wave + CHUNK,
+            ws = banded_select<VEC, G, R, OTF, S>(a, ni, inv_i, self, rs, e0, e1, s_sc, lds_wave + CHUNK,
                                                lds_wave + 2 * CHUNK, a.lowbits);
         } else {
             wave_lds_sync();
@@ -1364,7 +1375,7 @@ constexpr int FIN_SPIN_MAX = 1 << 19;
 constexpr int FIN_BLOCKS_MAX = 256;
 constexpr int FIN_GROUP_WORDS = 3 * CAND_MAX_K;      // LDS words of one row's winners: 32 keys (64 words) | 32 source ids
 
-template <int VEC, int G, int R, bool HEAD>
+template <int VEC, int G, int R, bool HEAD, typename S = float>
 __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, int rs, int deg, int t0, int nsel,
                                                 const unsigned long long *s_key_w, const int *s_src_w, int head_yy,
                                                 unsigned head_sv);
@@ -1435,7 +1446,7 @@ __device__ __forceinline__ void group_topk_keys_n(const unsigned long long (&key
 
 // Rows [pb, pb + 64 / G) of at most 128 candidates each, one per lane group.  seen (per group): the row's done
 // words were all read as done by the batch before (the look-ahead below); on return: whether row pb_next + gid's were.
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb_next, int *lds_wave, bool &dead,
                                                 bool &seen)
 {
@@ -1467,7 +1478,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
     if (!__all(ready)) dead = true;
     const bool run = act && ready;
     if (act && !ready)
-        for (int c = lg; c < a.C; c += G) a.out[(size_t)i * a.C + c] = __uint_as_float(0x7FC00000u);
+        for (int c = lg; c < a.C; c += G) a.out_at<S>((size_t)i * a.C + c) = __uint_as_float(0x7FC00000u);
     if (run)
         for (int t = t0 + lg; t < t1; t += G) st_agent(a.fin_done + t, 0ull);     // consumed (a replayed launch finds zeros)
     // look ahead: the next batch's done words, in flight under this batch's round trips (by now its tasks are
@@ -1520,7 +1531,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
 #pragma unroll
         for (int u = 0; u < STEP; ++u) {
             const int j = nsel > 0 ? s_src[min(w0 + u, nsel - 1)] : 0;
-            x[u].load(a.n + (size_t)j * a.C, a.C, lg);
+            x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
             nj[u] = a.nrm ? a.nrm[j] : 1.0f;
         }
 #pragma unroll
@@ -1546,7 +1557,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
         for (int g = 0; g < NG; g += 2 * m) part[g].add(part[g + m]);
     part[0].div((float)deg);
     row_epilogue<VEC, G, R>(a, part[0], i, lg);
-    if (run) part[0].store(a.out + (size_t)i * a.C, a.C, lg);
+    if (run) part[0].store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     seen = fwd_group_bits<G>(__ballot(mine_next), gid) == FULL;
     wave_lds_sync();            // the wave's LDS scratch is reused by its next batch
 }
@@ -1555,7 +1566,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
 // row, a lane per channel - in the finalize launch's own order (sixteen slices, slice s = tasks s, s + 16, .. added
 // in turn, then the slices in order: fin_cand_row / fin_wave_row), sixteen loads in flight.  seen / p_next: the
 // look-ahead of fin_group_batch.
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void fin_stream_row(const FwdArgs &a, int p, int p_next, bool &dead, bool &seen)
 {
     int lane = lane_id();
@@ -1575,7 +1586,7 @@ __device__ __forceinline__ void fin_stream_row(const FwdArgs &a, int p, int p_ne
     }
     if (!ready) {
         dead = true;
-        for (int c = lane; c < a.C; c += 64) a.out[(size_t)i * a.C + c] = __uint_as_float(0x7FC00000u);
+        for (int c = lane; c < a.C; c += 64) a.out_at<S>((size_t)i * a.C + c) = __uint_as_float(0x7FC00000u);
         return;
     }
     for (int t = t0 + lane; t < t1; t += 64) st_agent(a.fin_done + t, 0ull);      // consumed (a replayed launch finds zeros)
@@ -1604,7 +1615,7 @@ __device__ __forceinline__ void fin_stream_row(const FwdArgs &a, int p, int p_ne
         float sum = 0.f;
 #pragma unroll
         for (int u = 0; u < 16; ++u) sum += sl[u];
-        if (in) a.out[(size_t)i * a.C + c] = a.epilogue(sum / (float)deg, i, c);
+        if (in) a.out_at<S>((size_t)i * a.C + c) = a.epilogue(sum / (float)deg, i, c);
     }
     seen = __all(mine_next) != 0;
 }
@@ -1613,7 +1624,7 @@ __device__ __forceinline__ void fin_stream_row(const FwdArgs &a, int p, int p_ne
 // waves 2, 3 those of row p0 + 1 (none: they only keep the barriers company); the even wave of a pair merges.
 // Called by all waves of the workgroup - every wave passes the same three barriers whatever its row's state.
 // LDS per wave: its winners' keys [0, 64) words | source ids [64, 96) | count [96] | ready flag [97].
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_big, int (*lds)[WaveLds<G>::WORDS],
                                                bool &dead)
 {
@@ -1644,7 +1655,7 @@ __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_b
     if (act && !run) {
         dead = true;
         if (half == 0)
-            for (int c = lane; c < a.C; c += 64) a.out[(size_t)i * a.C + c] = __uint_as_float(0x7FC00000u);
+            for (int c = lane; c < a.C; c += 64) a.out_at<S>((size_t)i * a.C + c) = __uint_as_float(0x7FC00000u);
     }
     if (run && half == 0)
         for (int t = t0 + lane; t < t1; t += 64) st_agent(a.fin_done + t, 0ull);      // consumed (both waves have seen them)
@@ -1705,7 +1716,7 @@ __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_b
     const int nfin = __popcll(m0);
     if (k0) { const int o = prefix_popc(m0); s_key_w[o] = key0; s_src_w[o] = src0; }
     wave_lds_sync();
-    fin_winners_row<VEC, G, R, false>(a, p, i, rs, deg, t0, nfin, s_key_w, s_src_w, 0, 0u);
+    fin_winners_row<VEC, G, R, false, S>(a, p, i, rs, deg, t0, nfin, s_key_w, s_src_w, 0, 0u);
     wave_lds_sync();
 }
 
@@ -1720,11 +1731,12 @@ __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_b
 // without the small-row form: six spilled registers)
 // FIN: the launch's last workgroups finalize the split rows (role_task's note); its own instantiation, so the
 // launches without the role run the kernel they ran before it existed
-template <int VEC, int G, int R, bool FILT, bool OTF, int EPI = 0, bool FS = false, bool FIN = false>
+template <int VEC, int G, int R, bool FILT, bool OTF, int EPI = 0, bool FS = false, bool FIN = false, typename S = float>
 __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const FwdArgs a)
 {
     static_assert(!(FILT && OTF), "the filter belongs to the table mode");
     static_assert(FILT || !FS, "the small-row filter belongs to the FILT kernel");
+    static_assert(std::is_same<S, float>::value || (OTF && EPI == 0), "half rows: on the fly, no store epilogue");
     __shared__ __align__(16) int lds[WAVES][WaveLds<G>::WORDS];
     const int wave = threadIdx.x >> 6;
     int *lw = lds[wave];
@@ -1742,13 +1754,13 @@ __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const Fwd
         bool dead = false, seen = false;
         if (fa.k < 0) {                                       // (uniform) nothing selected: sums of partial rows
             for (int p = fb * WAVES + wave; p < fa.n_split; p += nfb * WAVES)
-                fin_stream_row<VEC, G, R>(fa, p, p + nfb * WAVES, dead, seen);
+                fin_stream_row<VEC, G, R, S>(fa, p, p + nfb * WAVES, dead, seen);
             return;
         }
         const int n_big = min(fa.n_split, fa.n_split_gt_wave);
-        for (int p0 = 2 * fb; p0 < n_big; p0 += 2 * nfb) fin_block_pair<VEC, G, R>(fa, p0, n_big, lds, dead);
+        for (int p0 = 2 * fb; p0 < n_big; p0 += 2 * nfb) fin_block_pair<VEC, G, R, S>(fa, p0, n_big, lds, dead);
         for (int pb = n_big + (fb * WAVES + wave) * RPW; pb < fa.n_split; pb += nfb * WAVES * RPW)
-            fin_group_batch<VEC, G, R>(fa, pb, pb + nfb * WAVES * RPW, lw, dead, seen);
+            fin_group_batch<VEC, G, R, S>(fa, pb, pb + nfb * WAVES * RPW, lw, dead, seen);
         // (Small-row sets kept back for these waves to take behind their rows - 400 .. 1 600 of 40 383 - moved
         // nothing: 50.9-51.6 us against 51.0; the launch is 6 % slower than without the role's 96 workgroups, the
         // share of the chip's wave slots they hold.)
@@ -1758,12 +1770,12 @@ __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const Fwd
     const int n_wave_rows = a.n_med_end - a.n_split;
     int it = blockIdx.x * WAVES + wave;
     for (; it < a.n_tasks; it += nw)
-        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN>(a, a.task_order[it], lw);
+        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN, S>(a, a.task_order[it], lw);
     it -= a.n_tasks;
     for (; it < n_wave_rows; it += nw)
-        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI>(a, it, lw);
+        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI, S>(a, it, lw);
     it -= n_wave_rows;
-    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS>(a, it, nw, nsets, lw);
+    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS, S>(a, it, nw, nsets, lw);
 }
 
 // ---------------------------------------------------------------------------
@@ -1792,7 +1804,7 @@ __device__ __forceinline__ int block_count(int c, FinShared &sh, int &parity)
     return tot;
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(FIN_BLOCK) void k_agg_fin(const FwdArgs a, int lds_scores)
 {
     using RowT = Row<VEC, G, R>;
@@ -1821,7 +1833,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_agg_fin(const FwdArgs a, int lds_
         for (int c = tid; c < a.C; c += FIN_BLOCK) {
             float s = 0.f;
             for (int t = t0; t < t1; ++t) s += a.partial[(size_t)t * a.C + c];
-            a.out[(size_t)i * a.C + c] = a.epilogue(s / (float)deg, i, c);
+            a.out_at<S>((size_t)i * a.C + c) = a.epilogue(s / (float)deg, i, c);
         }
         return;
     }
@@ -1898,7 +1910,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_agg_fin(const FwdArgs a, int lds_
                 const int idx = s_list[q];
                 const int j = a.col[rs + idx];
                 RowT x;
-                x.load(a.n + (size_t)j * a.C, a.C, lg);
+                x.load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
                 acc.axpy(sc[idx] * (a.nrm ? a.nrm[j] : 1.0f), x);        // (OTF: the rows are h itself)
             }
         }
@@ -1908,14 +1920,14 @@ __global__ __launch_bounds__(FIN_BLOCK) void k_agg_fin(const FwdArgs a, int lds_
         for (int ch = tid; ch < a.C; ch += FIN_BLOCK) {
             float s = 0.f;
             for (int w = 0; w < NW; ++w) s += s_part[(size_t)w * a.C + ch];
-            a.out[(size_t)i * a.C + ch] = a.epilogue(s / (float)deg, i, ch);
+            a.out_at<S>((size_t)i * a.C + ch) = a.epilogue(s / (float)deg, i, ch);
         }
     } else {
         // emit on a streaming row: the sum itself still comes from the partials
         for (int ch = tid; ch < a.C; ch += FIN_BLOCK) {
             float s = 0.f;
             for (int t = t0; t < t1; ++t) s += a.partial[(size_t)t * a.C + ch];
-            a.out[(size_t)i * a.C + ch] = a.epilogue(s / (float)deg, i, ch);
+            a.out_at<S>((size_t)i * a.C + ch) = a.epilogue(s / (float)deg, i, ch);
         }
     }
 }
@@ -1956,7 +1968,7 @@ __device__ __forceinline__ void fin_row_head(const FwdArgs &a, int i, int p, con
     }
 }
 
-template <int VEC, int G, int R, int NW, bool HEAD>
+template <int VEC, int G, int R, int NW, bool HEAD, typename S = float>
 __device__ __forceinline__ void fin_cand_row(const FwdArgs &a, int p, int max_slots, unsigned char *dyn)
 {
     using RowT = Row<VEC, G, R>;
@@ -1998,7 +2010,7 @@ __device__ __forceinline__ void fin_cand_row(const FwdArgs &a, int p, int max_sl
             float s = 0.f;
             for (int w = 0; w < FINC_WAVES_MAX; ++w) s += s_part[(size_t)w * a.C + c];
             if constexpr (HEAD) s_part[c] = s / (float)deg;     // (C <= 64 <= (NW * 64): the thread's own channel only)
-            else a.out[(size_t)i * a.C + c] = a.epilogue(s / (float)deg, i, c);
+            else a.out_at<S>((size_t)i * a.C + c) = a.epilogue(s / (float)deg, i, c);
         }
         if constexpr (HEAD) {
             __syncthreads();
@@ -2079,7 +2091,7 @@ __device__ __forceinline__ void fin_cand_row(const FwdArgs &a, int p, int max_sl
         if (q < nsel) {
             const int j = wsrc[q];
             RowT x;
-            x.load(a.n + (size_t)j * a.C, a.C, lg);
+            x.load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
             acc.axpy(key_score(win[q]) * (a.nrm ? a.nrm[j] : 1.0f), x);
         }
     }
@@ -2102,7 +2114,7 @@ __device__ __forceinline__ void fin_cand_row(const FwdArgs &a, int p, int max_sl
         float s = 0.f;
         for (int w = 0; w < NW; ++w) s += s_part[(size_t)w * a.C + ch];
         if constexpr (HEAD) s_part[ch] = s / (float)deg;
-        else a.out[(size_t)i * a.C + ch] = a.epilogue(s / (float)deg, i, ch);
+        else a.out_at<S>((size_t)i * a.C + ch) = a.epilogue(s / (float)deg, i, ch);
     }
     if constexpr (HEAD) {
         __syncthreads();
@@ -2110,20 +2122,21 @@ __device__ __forceinline__ void fin_cand_row(const FwdArgs &a, int p, int max_sl
     }
 }
 
-template <int VEC, int G, int R, int NW, bool HEAD>
+template <int VEC, int G, int R, int NW, bool HEAD, typename S = float>
 __global__ __launch_bounds__(NW * 64) void k_agg_fin_cand(const FwdArgs a, int max_slots)
 {
     extern __shared__ __align__(16) unsigned char dyn[];   // no static LDS in front of it
-    fin_cand_row<VEC, G, R, NW, HEAD>(a, blockIdx.x, max_slots, dyn);
+    fin_cand_row<VEC, G, R, NW, HEAD, S>(a, blockIdx.x, max_slots, dyn);
 }
 
 // The winners of a split row (s_key_w / s_src_w [0, nsel): keys and source ids, in the selection's own order) ->
 // the row's weighted sum, its mean and stores, the bookkeeping of the kept edges.  One wave.
-template <int VEC, int G, int R, bool HEAD>
+template <int VEC, int G, int R, bool HEAD, typename S>
 __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, int rs, int deg, int t0, int nsel,
                                                 const unsigned long long *s_key_w, const int *s_src_w, int head_yy,
                                                 unsigned head_sv)
 {
+    static_assert(std::is_same<S, float>::value || !HEAD, "the head reads fp32 rows");
     using RowT = Row<VEC, G, R>;
     constexpr int NG = 64 / G;
     const int lane = lane_id();
@@ -2139,7 +2152,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
         for (int u = 0; u < GU; ++u) {
             const int w = min(w0 + u * NG + gid, nsel - 1);
             const int j = s_src_w[w];
-            x[u].load(a.n + (size_t)j * a.C, a.C, lg);
+            x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
             nj[u] = a.nrm ? a.nrm[j] : 1.0f;
         }
 #pragma unroll
@@ -2169,7 +2182,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
         return;
     }
     row_epilogue<VEC, G, R>(a, acc, i, lg);
-    if (gid == 0) acc.store(a.out + (size_t)i * a.C, a.C, lg);
+    if (gid == 0) acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
 }
 
 // The same finalize for split rows whose candidates fit one wave-level selection
@@ -2177,7 +2190,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
 // barrier.  On graphs with many moderately large rows
 // (products-like: ~10^5 split rows) the 1024-thread tournament above is mostly idle.
 // s_key_w / s_src_w: the wave's own CAND_MAX_K LDS slots.
-template <int VEC, int G, int R, bool HEAD>
+template <int VEC, int G, int R, bool HEAD, typename S = float>
 __device__ __forceinline__ void fin_wave_row(const FwdArgs &a, int p, unsigned long long *s_key_w, int *s_src_w)
 {
     using RowT = Row<VEC, G, R>;
@@ -2202,7 +2215,7 @@ __device__ __forceinline__ void fin_wave_row(const FwdArgs &a, int p, unsigned l
             for (int u = 0; u < 16; ++u) s += v[u];
             for (int t = t0 + 16; t < t1; ++t) s += a.partial[(size_t)t * a.C + c];
             if constexpr (HEAD) s_row[c] = s / (float)deg;
-            else a.out[(size_t)i * a.C + c] = a.epilogue(s / (float)deg, i, c);
+            else a.out_at<S>((size_t)i * a.C + c) = a.epilogue(s / (float)deg, i, c);
         }
         if constexpr (HEAD) {
             if constexpr (VEC == 4 && R == 1 && (G == 8 || G == 16)) {
@@ -2232,11 +2245,11 @@ __device__ __forceinline__ void fin_wave_row(const FwdArgs &a, int p, unsigned l
     if (k0) { const int o = prefix_popc(m0); s_key_w[o] = key0; s_src_w[o] = src0; }
     if (k1) { const int o = n0 + prefix_popc(m1); s_key_w[o] = key1; s_src_w[o] = src1; }
     wave_lds_sync();
-    fin_winners_row<VEC, G, R, HEAD>(a, p, i, rs, deg, t0, nsel, s_key_w, s_src_w, head_yy, head_sv);
+    fin_winners_row<VEC, G, R, HEAD, S>(a, p, i, rs, deg, t0, nsel, s_key_w, s_src_w, head_yy, head_sv);
 }
 
 // 4 rows per 256-thread workgroup
-template <int VEC, int G, int R, bool HEAD>
+template <int VEC, int G, int R, bool HEAD, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_agg_fin_wave(const FwdArgs a, int first, int count)
 {
     __shared__ unsigned long long s_key[WAVES][CAND_MAX_K];
@@ -2244,7 +2257,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fin_wave(const FwdArgs a, int fir
     const int wave = threadIdx.x >> 6;
     const int q = blockIdx.x * WAVES + wave;
     if (q >= count) return;                                   // wave-uniform
-    fin_wave_row<VEC, G, R, HEAD>(a, first + q, s_key[wave], s_src[wave]);
+    fin_wave_row<VEC, G, R, HEAD, S>(a, first + q, s_key[wave], s_src[wave]);
 }
 // Both in ONE launch when the moderate split rows are few (arxiv-like graphs: a few hundred
 // split rows in all): workgroups [0, n_big) run the tournament of one big row each, the
@@ -2252,7 +2265,7 @@ __global__ __launch_bounds__(BLOCK) void k_agg_fin_wave(const FwdArgs a, int fir
 // tournaments of which 512 fit the chip (finalize 8.8 -> see DESIGN.md 4.1).
 // HEAD: its own instantiation (the head's code inside the plain one cost it 9 registers, 12 bytes of
 // scratch per lane and ~0.5 us of the headline step)
-template <int VEC, int G, int R, int NW, bool HEAD>
+template <int VEC, int G, int R, int NW, bool HEAD, typename S = float>
 __global__ __launch_bounds__(NW * 64) void k_agg_fin_mixed(const FwdArgs a, int max_slots, int n_big, int n_split,
                                                               int n_fin_blocks)
 {
@@ -2266,7 +2279,7 @@ __global__ __launch_bounds__(NW * 64) void k_agg_fin_mixed(const FwdArgs a, int 
         }
     }
     if ((int)blockIdx.x < n_big) {                         // (workgroup-uniform)
-        fin_cand_row<VEC, G, R, NW, HEAD>(a, blockIdx.x, max_slots, dyn);
+        fin_cand_row<VEC, G, R, NW, HEAD, S>(a, blockIdx.x, max_slots, dyn);
         return;
     }
     const int wave = threadIdx.x >> 6;
@@ -2274,7 +2287,7 @@ __global__ __launch_bounds__(NW * 64) void k_agg_fin_mixed(const FwdArgs a, int 
     if (p >= n_split) return;                              // wave-uniform
     unsigned long long *s_key = reinterpret_cast<unsigned long long *>(dyn) + wave * CAND_MAX_K;
     int *s_src = reinterpret_cast<int *>(dyn + NW * CAND_MAX_K * 8) + wave * CAND_MAX_K;
-    fin_wave_row<VEC, G, R, HEAD>(a, p, s_key, s_src);
+    fin_wave_row<VEC, G, R, HEAD, S>(a, p, s_key, s_src);
 }
 
 // whether split rows keep chunk-local candidates (else: scores to HBM scratch + k_agg_fin)
@@ -2319,7 +2332,7 @@ inline int finc_waves(const FwdArgs &a, int max_split_deg)
 }
 
 // the candidate finalize's launches at NW waves per workgroup
-template <int VEC, int G, int R, int NW, bool HEAD>
+template <int VEC, int G, int R, int NW, bool HEAD, typename S = float>
 int launch_cand_finalize(const FwdArgs &a, int max_split_deg, hipStream_t st)
 {
     const int max_tasks = ceil_div(max_split_deg, CHUNK);
@@ -2327,7 +2340,7 @@ int launch_cand_finalize(const FwdArgs &a, int max_split_deg, hipStream_t st)
     const size_t dyn = finc_lds_bytes(a.C, max_slots, NW);
     if (dyn > FINC_LDS_BUDGET) { set_error("internal: candidate finalize does not fit LDS"); return SNGNN_EINVAL; }
     if (dyn > 48 * 1024)
-        SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin_cand<VEC, G, R, NW, HEAD>,
+        SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin_cand<VEC, G, R, NW, HEAD, S>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     const FinShape fs = finalize_shape(a);
     const int n_wave = fs.n_wave, n_big = fs.n_big, n_big_true = fs.n_big_true;
@@ -2335,32 +2348,33 @@ int launch_cand_finalize(const FwdArgs &a, int max_split_deg, hipStream_t st)
         // few moderate rows: one mixed launch
         const size_t dyn_mixed = std::max(dyn, (size_t)NW * CAND_MAX_K * 12);
         if (dyn_mixed > 48 * 1024)
-            SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin_mixed<VEC, G, R, NW, HEAD>,
+            SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin_mixed<VEC, G, R, NW, HEAD, S>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_mixed));
         const int n_fin_blocks = n_big_true + ceil_div(n_wave, NW);
         const int n_head_blocks = HEAD ? a.head_nmain : 0;
-        k_agg_fin_mixed<VEC, G, R, NW, HEAD><<<n_fin_blocks + n_head_blocks, NW * 64, dyn_mixed, st>>>(
+        k_agg_fin_mixed<VEC, G, R, NW, HEAD, S><<<n_fin_blocks + n_head_blocks, NW * 64, dyn_mixed, st>>>(
             a, max_slots, n_big_true, a.n_split, n_fin_blocks);
     } else {
         if constexpr (HEAD) launch_head_rows<VEC, G, R>(a, st);
-        if (n_big > 0) k_agg_fin_cand<VEC, G, R, NW, HEAD><<<n_big, NW * 64, dyn, st>>>(a, max_slots);
+        if (n_big > 0) k_agg_fin_cand<VEC, G, R, NW, HEAD, S><<<n_big, NW * 64, dyn, st>>>(a, max_slots);
         if (a.n_split > n_big)
-            k_agg_fin_wave<VEC, G, R, HEAD><<<ceil_div(a.n_split - n_big, WAVES), BLOCK, 0, st>>>(a, n_big, a.n_split - n_big);
+            k_agg_fin_wave<VEC, G, R, HEAD, S><<<ceil_div(a.n_split - n_big, WAVES), BLOCK, 0, st>>>(a, n_big, a.n_split - n_big);
     }
     return SNGNN_OK;
 }
 
 // launches of the split rows' finalize (after their tasks, same stream)
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 int launch_split_finalize(const FwdArgs &a, int max_split_deg, hipStream_t st)
 {
+    constexpr bool F32 = std::is_same<S, float>::value;         // (half rows: no head - the host refuses it)
     if (a.n_split > 0 && a.use_cand) {
         // streaming rows and candidate tournament
-        if constexpr (VEC == 4 && R == 1 && (G == 8 || G == 16)) {
+        if constexpr (F32 && VEC == 4 && R == 1 && (G == 8 || G == 16)) {
             if (a.head_sel) return launch_cand_finalize<VEC, G, R, 8, true>(a, max_split_deg, st);
         }
-        if (finc_waves(a, max_split_deg) == 16) return launch_cand_finalize<VEC, G, R, 16, false>(a, max_split_deg, st);
-        return launch_cand_finalize<VEC, G, R, 8, false>(a, max_split_deg, st);
+        if (finc_waves(a, max_split_deg) == 16) return launch_cand_finalize<VEC, G, R, 16, false, S>(a, max_split_deg, st);
+        return launch_cand_finalize<VEC, G, R, 8, false, S>(a, max_split_deg, st);
     } else if (a.n_split > 0) {
         const size_t fixed = (size_t)a.C * (FIN_BLOCK / 64) * 4 + (size_t)std::min(std::max(a.k, 0), max_split_deg) * 4;
         const size_t budget = 120 * 1024;
@@ -2369,11 +2383,11 @@ int launch_split_finalize(const FwdArgs &a, int max_split_deg, hipStream_t st)
         if (fixed < budget) lds_scores = (int)std::min<size_t>((budget - fixed) / 4, (size_t)max_split_deg);
         const size_t dyn = fixed + (size_t)lds_scores * 4;
         if (dyn > 48 * 1024)
-            SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin<VEC, G, R>,
+            SN_HIP(hipFuncSetAttribute((const void *)k_agg_fin<VEC, G, R, S>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        k_agg_fin<VEC, G, R><<<a.n_split, FIN_BLOCK, dyn, st>>>(a, lds_scores);      // (no head there: the host refuses)
+        k_agg_fin<VEC, G, R, S><<<a.n_split, FIN_BLOCK, dyn, st>>>(a, lds_scores);      // (no head there: the host refuses)
     } else {
-        launch_head_rows<VEC, G, R>(a, st);
+        if constexpr (F32) launch_head_rows<VEC, G, R>(a, st);
     }
     return SNGNN_OK;
 }
@@ -2386,9 +2400,10 @@ extern int g_prof_reps;
 extern int g_fin_inline, g_last_fin_blocks;
 unsigned long long next_fin_nonce();
 
-template <int VEC, int G, int R, int EPI>
+template <int VEC, int G, int R, int EPI, typename S = float>
 int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hipStream_t st)
 {
+    constexpr bool F32 = std::is_same<S, float>::value;        // (half rows: on the fly only, launcher's check)
     const int reps = ev ? std::max(g_prof_reps, 1) : 1;
     constexpr int RPW = 64 / G;
     const int n_small = a0.N - a0.n_med_end;
@@ -2452,24 +2467,24 @@ int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hi
     if (ev) SN_HIP(hipEventRecord(ev[0], st));
 #define SNGNN_FWD_LAUNCH(FILTV, OTFV, FSV)                                                              \
     do {                                                                                              \
-        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true><<<grid, BLOCK, 0, st>>>(a);  \
-        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false><<<grid, BLOCK, 0, st>>>(a);            \
+        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true, S><<<grid, BLOCK, 0, st>>>(a); \
+        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false, S><<<grid, BLOCK, 0, st>>>(a);           \
     } while (0)
     for (int rep = 0; rep < reps && grid > 0; ++rep) {
-        if (a.nrm == nullptr) {                                  // OTF: a.n holds the raw rows
+        if (!F32 || a.nrm == nullptr) {                          // OTF: a.n holds the raw rows
             SNGNN_FWD_LAUNCH(false, true, false);
-        } else if constexpr (VEC == 4 && G >= 16 && G * R <= 128) {     // the (G, R) that C in 36 .. 512 maps to
+        } else if constexpr (F32 && VEC == 4 && G >= 16 && G * R <= 128) {     // the (G, R) that C in 36 .. 512 maps to
             if (a.filt && a.k >= 0 && a.filt_small) SNGNN_FWD_LAUNCH(true, false, true);
             else if (a.filt && a.k >= 0) SNGNN_FWD_LAUNCH(true, false, false);
             else SNGNN_FWD_LAUNCH(false, false, false);
-        } else {
+        } else if constexpr (F32) {
             SNGNN_FWD_LAUNCH(false, false, false);
         }
     }
 #undef SNGNN_FWD_LAUNCH
     if (ev) SN_HIP(hipEventRecord(ev[1], st));
     for (int rep = 0; rep < reps && !fin_inline; ++rep)
-        if (int rc = launch_split_finalize<VEC, G, R>(a, max_split_deg, st)) return rc;
+        if (int rc = launch_split_finalize<VEC, G, R, S>(a, max_split_deg, st)) return rc;
     if (ev) {
         SN_HIP(hipEventRecord(ev[2], st));
         SN_HIP(hipEventRecord(ev[3], st));       // empty interval: the cost of an event pair
@@ -2491,6 +2506,16 @@ int launch_agg_fwd_epi(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipS
 {
     return launch_agg_fwd_impl<VEC, G, R, 1>(a, max_split_deg, ev, st);
 }
+// the half path (sngnn_agg_forward_half): rows h stored as S = __half / __hip_bfloat16, scored on the fly, out
+// stored as S.  The kernels are the fp32 ones with their row loads and output stores in S (device_utils.h: Row),
+// so every register holds what it holds in the fp32 forward of h.float(): same lanes, same order, same bits.
+template <typename S> struct LaunchHalf {
+    template <int VEC, int G, int R>
+    static int run(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
+    {
+        return launch_agg_fwd_impl<VEC, G, R, 0, S>(a, max_split_deg, ev, st);
+    }
+};
 
 
 // one translation unit per VEC instantiates these
@@ -2509,5 +2534,12 @@ int launch_normalize_v2(const RowCfg &cfg, const float *h, int64_t rows, int C, 
 int launch_normalize_v4(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
                         hipStream_t st);
 int launch_filter_v4(const RowCfg &cfg, const float *n, int64_t rows, int C, void *filt, hipStream_t st);
+// the half path, one translation unit per storage type and VEC (agg_fwd_f16_v*.hip, agg_fwd_bf16_v*.hip)
+int launch_agg_fwd_f16_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_f16_v2(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_f16_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_bf16_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_bf16_v2(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_bf16_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
 
 }  // namespace sngnn

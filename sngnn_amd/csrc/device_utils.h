@@ -1,5 +1,8 @@
 // Device-side helpers shared by the aggregation kernels (gfx950, wave = 64).
 #pragma once
+#include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+#include <type_traits>
 #include "common.h"
 
 namespace sngnn {
@@ -266,8 +269,37 @@ __device__ __forceinline__ void split_bf16x4(const float (&v)[4], sn_u32x2 &p1, 
 __device__ __forceinline__ float ieee_sqrt(float x) { return __builtin_sqrtf(x); }
 __device__ __forceinline__ float ieee_div(float a, float b) { return a / b; }
 
+// Half-width storage of feature rows (sngnn_agg_forward_half / sngnn_agg_backward_half): the 16-bit pattern ->
+// its fp32 value (exact: every fp16 and bf16 value is an fp32 value), and fp32 -> the pattern, rounded to nearest
+// even, once.  The kernels run their fp32 arithmetic unchanged between the two.
+template <typename S> struct Half16;
+template <> struct Half16<__half> {
+    static __device__ __forceinline__ float widen(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
+    static __device__ __forceinline__ unsigned short narrow(float v)
+    {
+        return __builtin_bit_cast(unsigned short, (_Float16)v);        // v_cvt_f16_f32: round to nearest even
+    }
+};
+template <> struct Half16<__hip_bfloat16> {
+    static __device__ __forceinline__ float widen(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
+    static __device__ __forceinline__ unsigned short narrow(float v)
+    {
+        const unsigned u = __float_as_uint(v);
+        if (v != v) return (unsigned short)0x7FC0u;                     // NaN stays a (quiet) NaN
+        return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);   // round to nearest even
+    }
+};
+
+// one element of a half-width output row: `ref = v` stores v rounded to S
+template <typename S> struct HalfRef {
+    S *p;
+    __device__ __forceinline__ void operator=(float v) const { *reinterpret_cast<unsigned short *>(p) = Half16<S>::narrow(v); }
+};
+
 // One node row spread over the G lanes of a group: lane lg holds VEC consecutive
 // channels per step, R steps.  Channels beyond C read as zero.
+// Rows stored as __half / __hip_bfloat16 load into (and store from) the same fp32 registers, in the same
+// lanes: VEC * 2 bytes per lane instead of VEC * 4.
 template <int VEC, int G, int R> struct Row {
     float x[R][VEC];
 
@@ -299,6 +331,57 @@ template <int VEC, int G, int R> struct Row {
             } else {
                 const float t = row[cc];
                 x[r][0] = in ? t : 0.f;
+            }
+        }
+    }
+
+    template <typename S> __device__ __forceinline__ void load(const S *__restrict__ row, int C, int lg)
+    {
+        static_assert(sizeof(S) == 2, "half-width rows: __half or __hip_bfloat16");
+        const unsigned short *p = reinterpret_cast<const unsigned short *>(row);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int c0 = (r * G + lg) * VEC;
+            const bool in = c0 < C;
+            const int cc = in ? c0 : 0;
+            if constexpr (VEC == 4) {
+                // (a native two-word vector: through HIP's uint2 the compiler split some of these 8-byte loads into
+                // two dword loads - twice the memory instructions, 25 % on the backward at arxiv size)
+                const sn_u32x2 t = *reinterpret_cast<const sn_u32x2 *>(p + cc);
+                const unsigned lo = t[0], hi = t[1];
+                x[r][0] = in ? Half16<S>::widen((unsigned short)(lo & 0xFFFFu)) : 0.f;
+                x[r][1] = in ? Half16<S>::widen((unsigned short)(lo >> 16)) : 0.f;
+                x[r][2] = in ? Half16<S>::widen((unsigned short)(hi & 0xFFFFu)) : 0.f;
+                x[r][3] = in ? Half16<S>::widen((unsigned short)(hi >> 16)) : 0.f;
+            } else if constexpr (VEC == 2) {
+                const unsigned t = *reinterpret_cast<const unsigned *>(p + cc);
+                x[r][0] = in ? Half16<S>::widen((unsigned short)(t & 0xFFFFu)) : 0.f;
+                x[r][1] = in ? Half16<S>::widen((unsigned short)(t >> 16)) : 0.f;
+            } else {
+                const unsigned short t = p[cc];
+                x[r][0] = in ? Half16<S>::widen(t) : 0.f;
+            }
+        }
+    }
+
+    template <typename S> __device__ __forceinline__ void store(S *__restrict__ row, int C, int lg) const
+    {
+        static_assert(sizeof(S) == 2, "half-width rows: __half or __hip_bfloat16");
+        unsigned short *p = reinterpret_cast<unsigned short *>(row);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int c0 = (r * G + lg) * VEC;
+            if (c0 < C) {
+                if constexpr (VEC == 4) {
+                    const sn_u32x2 t = {(unsigned)Half16<S>::narrow(x[r][0]) | ((unsigned)Half16<S>::narrow(x[r][1]) << 16),
+                                        (unsigned)Half16<S>::narrow(x[r][2]) | ((unsigned)Half16<S>::narrow(x[r][3]) << 16)};
+                    *reinterpret_cast<sn_u32x2 *>(p + c0) = t;
+                } else if constexpr (VEC == 2) {
+                    *reinterpret_cast<unsigned *>(p + c0) =
+                        (unsigned)Half16<S>::narrow(x[r][0]) | ((unsigned)Half16<S>::narrow(x[r][1]) << 16);
+                } else {
+                    p[c0] = Half16<S>::narrow(x[r][0]);
+                }
             }
         }
     }

@@ -122,6 +122,14 @@ def current_partition() -> Optional[Partition]:
     return _current
 
 
+def check_features(x: torch.Tensor) -> None:
+    """Feature rows under a node-range partition are float32: the half path (float16 / bfloat16 rows,
+    ops.aggregate) runs on one GPU only."""
+    if x.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError(f"features of dtype {x.dtype} under a node-range partition: the half path runs on one GPU "
+                        "only (cast the model and its features to torch.float32)")
+
+
 def _host_staged(t: torch.Tensor, group=None) -> bool:
     """Whether the collective on ``t`` has to go through host copies: gloo moves host memory only,
     so a multi-rank REHEARSAL on a box with fewer GPUs than ranks (GPU tensors, gloo group) stages

@@ -49,14 +49,16 @@ class _Stack(nn.Module):
         # produces their operand, and backward as the store epilogue of the next ``lin``'s input
         # gradient (ops.HiddenEpilogue) - without batch norm in between, on one GPU, for the layers
         # that take it (SNConv, SNConv_plus); everything else runs the reference's op sequence
+        # (half features - a model cast to float16 / bfloat16 - take the plain op sequence: the half path of the
+        # aggregation has no store epilogue)
         fusable = (FUSE_HIDDEN and not self.bn and sn_dist.current_partition() is None and x.is_cuda
-                   and isinstance(self.lins[0], (SNConv, SNConv_plus, SNConv_plus_plus)))
+                   and x.dtype == torch.float32 and isinstance(self.lins[0], (SNConv, SNConv_plus, SNConv_plus_plus)))
         # EVALUATION with batch norm (models.py:207-208): the running statistics are constants, so the norm is a
         # per-channel scale and shift - folded into the NEXT conv's ``lin`` (conv.LinFold) - and the conv's bias
         # + relu in front of it go into the aggregation's store epilogue: no elementwise pass is left between two
         # conv layers.  (Training-mode batch norm needs the batch's statistics: the op sequence below.)
         if (FUSE_HIDDEN and self.bn and not self.training and sn_dist.current_partition() is None and x.is_cuda
-                and isinstance(self.lins[0], (SNConv, SNConv_plus))):
+                and x.dtype == torch.float32 and isinstance(self.lins[0], (SNConv, SNConv_plus))):
             return self._forward_logits_bn_eval(x, edge_index, head)
         act = None
         seeds = self._dropout_seeds(x.device) if (fusable and len(self.lins) > 1 and self.training

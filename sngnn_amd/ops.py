@@ -15,8 +15,15 @@ from . import _lib
 from .graph import Graph
 
 
-def _check_rows(t: torch.Tensor, n: int, what: str) -> torch.Tensor:
-    if t.dtype != torch.float32:
+# storage types of the half path (sngnn_agg_forward_half / sngnn_agg_backward_half): the fp32 operator on
+# h.float(), only the stored rows rounded once to the type
+HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+def _check_rows(t: torch.Tensor, n: int, what: str, half: bool = False) -> torch.Tensor:
+    if t.dtype != torch.float32 and not (half and t.dtype in HALF_DTYPES):
+        if half:
+            raise ValueError(f"{what} must be float32, float16 or bfloat16, got {t.dtype}")
         raise ValueError(f"{what} must be float32 (the reference path is fp32 only)")
     if not t.is_cuda:
         raise ValueError(f"{what} must live on the GPU (there is no CPU path)")
@@ -34,15 +41,17 @@ def _stream(device) -> int:
 def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: float, *,
                       save_for_backward: bool = False, want_selection: bool = False):
     """Returns (out, wsel, inv_norm, sel_src, sel_w); the optional ones are None
-    unless requested.  ``top_k=None`` is SNConv (no selection)."""
+    unless requested.  ``top_k=None`` is SNConv (no selection).  A float16 / bfloat16 ``h`` takes
+    the half path: ``out`` in h's dtype (the fp32 operator on h.float(), scored on the fly, its
+    rows rounded once), everything else fp32."""
     lib = _lib.load()
     n = graph.num_nodes
-    h = _check_rows(h, graph.num_total_nodes, "h")
+    h = _check_rows(h, graph.num_total_nodes, "h", half=True)
     c = h.size(1)
     k = -1 if top_k is None else int(top_k)
     if top_k is not None and k < 0:
         raise ValueError("top_k must be >= 0")
-    out = torch.empty((n, c), dtype=torch.float32, device=h.device)
+    out = torch.empty((n, c), dtype=h.dtype, device=h.device)
     wsel = inv = sel_src = sel_w = None
     if save_for_backward:
         wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=h.device)
@@ -53,6 +62,13 @@ def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: 
         sel_src = torch.empty((n, k), dtype=torch.int32, device=h.device)
         sel_w = torch.empty((n, k), dtype=torch.float32, device=h.device)
     ws = graph.workspace(c)
+    if h.dtype in HALF_DTYPES:
+        with torch.cuda.device(h.device):
+            rc = lib.sngnn_agg_forward_half(graph.handle, h.data_ptr(), HALF_DTYPES[h.dtype], c, k, float(thr),
+                                            out.data_ptr(), _lib.ptr(wsel), _lib.ptr(inv), _lib.ptr(sel_src),
+                                            _lib.ptr(sel_w), ws.data_ptr(), _stream(h.device))
+        _lib.check(rc, "sngnn_agg_forward_half")
+        return out, wsel, inv, sel_src, sel_w
     with torch.cuda.device(h.device):
         rc = lib.sngnn_agg_forward(graph.handle, h.data_ptr(), c, k, float(thr), out.data_ptr(),
                                    _lib.ptr(wsel), _lib.ptr(inv), _lib.ptr(sel_src),
@@ -166,13 +182,27 @@ def aggregate_forward_normalized(graph: Graph, n: torch.Tensor, nrm: torch.Tenso
 def aggregate_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
                        wsel: torch.Tensor, top_k: Optional[int] = None) -> torch.Tensor:
     """``top_k``: the forward's top_k (a bound on the kept in-edges per row; lets the library
-    take every node in one launch) or None when unknown / nothing was selected."""
+    take every node in one launch) or None when unknown / nothing was selected.  A float16 /
+    bfloat16 ``h`` (and ``grad_out`` of the same dtype) takes the half path: ``grad_h`` in that dtype,
+    the fp32 backward on the widened rows rounded once."""
     lib = _lib.load()
-    h = _check_rows(h, graph.num_total_nodes, "h")
-    grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out")
+    h = _check_rows(h, graph.num_total_nodes, "h", half=True)
+    grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out", half=True)
     c = h.size(1)
     grad_h = torch.empty_like(h)
     ws = graph.workspace(c)
+    if h.dtype in HALF_DTYPES:
+        if grad_out.dtype != h.dtype:
+            raise ValueError(f"grad_out must have h's dtype {h.dtype}, got {grad_out.dtype}")
+        with torch.cuda.device(h.device):
+            rc = lib.sngnn_agg_backward_half(graph.handle, h.data_ptr(), HALF_DTYPES[h.dtype], c,
+                                             grad_out.data_ptr(), wsel.data_ptr(),
+                                             -1 if top_k is None else int(top_k), grad_h.data_ptr(),
+                                             ws.data_ptr(), _stream(h.device))
+        _lib.check(rc, "sngnn_agg_backward_half")
+        return grad_h
+    if grad_out.dtype != torch.float32:
+        raise ValueError("grad_out must be float32 (the reference path is fp32 only)")
     with torch.cuda.device(h.device):
         rc = lib.sngnn_agg_backward_topk(graph.handle, h.data_ptr(), c, grad_out.data_ptr(),
                                          wsel.data_ptr(), -1 if top_k is None else int(top_k),
@@ -296,6 +326,17 @@ class _Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, graph, top_k, thr, unit=None, epi=None, bias=None, head=None):
         need_grad = ctx.needs_input_grad[0]
+        if h.dtype in HALF_DTYPES:
+            # the half path: the plain on-the-fly forward; the caller runs bias / relu / dropout / head in torch
+            if unit is not None or epi is not None or bias is not None or head is not None:
+                raise ValueError(f"h of dtype {h.dtype}: no unit rows, store epilogue, bias or head "
+                                 "(the half path is the plain aggregation)")
+            ctx.epi, ctx.bits, ctx.bias_grad = None, False, False
+            out, wsel, _, _, _ = aggregate_forward(graph, h, top_k, thr, save_for_backward=need_grad)
+            if need_grad:
+                ctx.graph, ctx.top_k = graph, top_k
+                ctx.save_for_backward(h, wsel)
+            return out
         ctx.epi = epi
         # training calls: where the library can, the forward writes WHICH edges it kept as packed bits
         # itself (sngnn_epilogue_t.kept_bits) - no per-edge weights, no packing launch in the backward

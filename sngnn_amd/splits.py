@@ -240,6 +240,10 @@ class ReplicaBatch(nn.Module):
 
     def __init__(self, template, replicas: int):
         super().__init__()
+        for name, p in template.named_parameters():
+            if p.dtype != torch.float32:
+                raise TypeError(f"ReplicaBatch needs a float32 template: parameter {name} is {p.dtype} "
+                                "(train a half model with the eager train())")
         lin = template.lins[0].lin
         self.kind = type(template)
         self.R = int(replicas)
@@ -491,6 +495,9 @@ def train_splits(batch: ReplicaBatch, data, masks, optimizer, epochs: int, patie
     extra and its reported numbers are frozen at its stop): its FINAL parameters in ``batch`` are therefore
     not those it had at its stop epoch.  Like ``train_graphed``, pass freshly initialised models' values
     when the trajectory must match."""
+    if data.x.dtype != torch.float32:
+        raise TypeError(f"train_splits needs float32 features, got {data.x.dtype} (train a half model with the eager "
+                        "train())")
     se = SplitsEpoch(batch, data, masks, optimizer, warmup=0)
     stop = EarlyStopping(batch.R, patience, se.counts)
     dur = []

@@ -77,6 +77,17 @@ def train(model, data, optimizer, epochs: int, patience: int, log=None) -> Dict:
                 mean_epoch_s=sum(dur) / max(len(dur), 1))
 
 
+def check_float32(model, x: torch.Tensor, what: str) -> None:
+    """Captured epochs and replica batches run float32 models only (their fused launches - lin's epilogue, the head,
+    the kept bits - have no half form): a TypeError that names the dtype for a model cast to float16 / bfloat16."""
+    for name, p in model.named_parameters():
+        if p.dtype != torch.float32:
+            raise TypeError(f"{what} needs a float32 model: parameter {name} is {p.dtype} "
+                            "(train a half model with the eager train())")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what} needs float32 features, got {x.dtype} (train a half model with the eager train())")
+
+
 class GraphedEpoch:
     """One full epoch (train step + validation + test passes) captured in a HIP graph.
 
@@ -92,6 +103,7 @@ class GraphedEpoch:
     """
 
     def __init__(self, model, data, optimizer, warmup: int = 3, share_eval_forward: bool = True):
+        check_float32(model, data.x, "GraphedEpoch")
         self.model, self.data, self.opt = model, data, optimizer
         # validate_step and test_step (train.py:92-117) run the SAME eval-mode forward - same
         # parameters, same data, no dropout, batch-norm on its running statistics - and differ only
