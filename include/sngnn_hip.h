@@ -287,7 +287,8 @@ int sngnn_agg_forward_rows(const sngnn_graph_t *g, const float *n, const float *
  * chain of round trips fits under the launch's own time (arxiv-sized graphs and up; calls that rank from
  * candidates, no head epilogue), else in a launch of its own; 0 = always a launch of its own; v > 1 = inside the
  * main launch on v workgroups.  Same selections and kept weights either way; the rows' sums agree bit for bit for
- * rows of at most 128 candidates and to rounding (another summation order) for the bigger ones. */
+ * rows of at most 128 candidates and to rounding (another summation order) for the bigger ones;
+ * knob 10 = copies of sngnn_cosine_hist's counter table in LDS (see there). */
 int sngnn_tuning_set(int which, int value);
 /* how many workgroups of the last sngnn_agg_forward* launch on this process finalized split rows (0 = the
  * finalize was a launch of its own, or there was nothing to finalize) - measurement aid, see knob 9 */
@@ -617,6 +618,30 @@ int sngnn_cosine_dense(const float *x, int64_t N, int64_t F, float *S, void *str
 int sngnn_cosine_class_sums(const float *x, int64_t N, int64_t F, const int32_t *y,
                             int n_classes, double *class_sum, double *diag_sum,
                             void *stream);
+/*
+ * The distribution the reference's toolbox draws (plot.py:61: `sns.distplot(sim, bins=200)` on the `sim` of
+ * dense.py:144-149) at any N - where dense.py:9-30 returns `None, mean` and nothing can be drawn: the histogram of
+ * the N (N - 1) off-diagonal entries of S = normalize(x) normalize(x)^T in one scan of x, S never stored (the tile
+ * engine of sngnn_knn_graph on the upper triangle, each pair counted twice; fp32 rounding: exact bf16 split or
+ * fp32 MFMAs, knob 5).
+ *   y       dev i32 [N] or NULL.  With y the counters have two rows: row 0 pairs with y_i == y_j, row 1 pairs
+ *           with y_i != y_j; a NEGATIVE label is "unlabelled" and every pair with such a node counts in row 1.
+ *   edges   dev f32 [bins + 1], ascending (not checked here); 1 <= bins <= 1024.  Value s belongs to bin b with
+ *           edges[b] <= s < edges[b + 1], the last bin closed on the right (numpy's rule) - decided against this
+ *           table itself, not against a formula.
+ *   counts  dev u64 [groups][bins + 2], groups = y ? 2 : 1: slot 0 = values below edges[0], slots 1 .. bins the
+ *           bins, slot bins + 1 = values above edges[bins].  Ordered pairs: a row block sums to the number of
+ *           its pairs, all of them to N (N - 1).
+ *   stats   dev f64 [3]: min, max (fp32 values) and sum (f64) of the counted entries.
+ * Both outputs are overwritten (no zeroing by the caller); N <= 1: counts 0, stats = +inf, -inf, 0.  Only
+ * enqueues on `stream`; integer atomics and fixed-order reductions: the same bits on every run.
+ *   workspace: sngnn_cosine_hist_workspace_bytes(N, F, bins, groups)
+ * Knob 10 of sngnn_tuning_set (measurement): copies of the per-workgroup counter table in LDS, 0 (default) = as
+ * many as fit up to 16, 1 = one (plain same-address LDS atomics), 2 / 4 / 8 / 16.
+ */
+int64_t sngnn_cosine_hist_workspace_bytes(int64_t N, int64_t F, int bins, int groups);
+int sngnn_cosine_hist(const float *x, int64_t N, int64_t F, const int32_t *y, const float *edges, int bins,
+                      unsigned long long *counts, double *stats, void *workspace, void *stream);
 /*
  * dense.py:152-164: per-edge cosine of raw features for an arbitrary COO edge
  * list: sim[e] = <n[a_e], n[b_e]>, a = edge_index[0], b = edge_index[1].

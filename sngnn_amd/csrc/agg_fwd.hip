@@ -87,7 +87,8 @@ unsigned long long sngnn::next_fin_nonce()
 bool sngnn::fwd_scores_on_the_fly_forced() { return g_table_mode == 2; }
 extern "C" int sngnn_tuning_set(int which, int value)
 {
-    SN_REQUIRE(which == 0 || (which >= 2 && which <= 9), SNGNN_EINVAL, "unknown tuning knob");
+    SN_REQUIRE(which == 0 || (which >= 2 && which <= 10), SNGNN_EINVAL, "unknown tuning knob");
+    if (which == 10) return sngnn::set_hist_copies(value);
     if (which == 9) { sngnn::g_fin_inline = value < 0 ? 0 : value; return SNGNN_OK; }
     if (which == 8) { g_filt_min_deg = value; return SNGNN_OK; }
     if (which == 7) return sngnn::set_cosine_split(value);

@@ -46,6 +46,7 @@ int set_bwd_roles(int v);
 int set_lin_mode(int v);       // linear.hip (knob 5)
 int set_knn_route(int v);      // knn.hip (knob 6)
 int set_cosine_split(int v);   // toolbox.hip (knob 7)
+int set_hist_copies(int v);    // cosine_hist.hip (knob 10)
 bool fp32_mfma_only();         // knob 5 == 1: the fp32 contractions stay on fp32 MFMAs
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

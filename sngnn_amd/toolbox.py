@@ -8,6 +8,8 @@ column-normalised input stays sparse on the GPU); plot.py is not (matplotlib, ou
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import _lib
@@ -89,7 +91,8 @@ def node_similarity_dense_large_parted(x, corrected: bool = False):
     """dense.py:9-30 without the 1000-row block loops.  The reference's last line
     has an operator-precedence slip, ``(sum - N) / (N - 1) * N`` (dense.py:28); that
     value is returned by default, ``corrected=True`` gives the mean over the
-    N (N - 1) off-diagonal pairs."""
+    N (N - 1) off-diagonal pairs.  The first result stays ``None`` as in the reference;
+    ``node_similarity_histogram`` gives the distribution of those pairs at any N."""
     x = _x(x)
     n = x.size(0)
     sums, diag = class_block_sums(x, torch.zeros(n, dtype=torch.int32, device=x.device), 1)
@@ -97,6 +100,98 @@ def node_similarity_dense_large_parted(x, corrected: bool = False):
     if corrected:      # the true diagonal: all-zero rows contribute 0, not 1
         return None, ((total - diag[0]) / (n * (n - 1))).to(torch.float32)
     return None, ((total - n) / (n - 1) * n).to(torch.float32)
+
+
+class SimilarityHistogram(NamedTuple):
+    """``node_similarity_histogram``'s result: ``counts`` int64 [bins] (or [2, bins] with labels: row 0 pairs
+    of equal label, row 1 the others), ``edges`` fp32 [bins + 1], ``outside`` int64 [..., 2] (values below
+    ``edges[0]`` / above ``edges[-1]``), ``minimum`` / ``maximum`` (0-d fp32) and ``mean`` (0-d f64) of all
+    N (N - 1) off-diagonal cosines."""
+    counts: torch.Tensor
+    edges: torch.Tensor
+    outside: torch.Tensor
+    minimum: torch.Tensor
+    maximum: torch.Tensor
+    mean: torch.Tensor
+
+
+HIST_MAX_BINS = 1024
+
+
+def _hist_edges(lo, hi, bins, device):
+    """``torch.linspace(lo, hi, bins + 1, dtype=float64)`` rounded to fp32; made on the device, so a fixed-range
+    call does no host copy and can be captured in a graph.  (The kernel bins against this very table.)"""
+    return torch.linspace(lo, hi, bins + 1, dtype=torch.float64, device=device).to(torch.float32)
+
+
+def _hist_scan(x, y32, edges, bins):
+    n, f = x.shape
+    lib = _lib.load()
+    groups = 1 if y32 is None else 2
+    counts = torch.empty((groups, bins + 2), dtype=torch.int64, device=x.device)
+    stats = torch.empty(3, dtype=torch.float64, device=x.device)
+    ws = torch.empty(max(int(lib.sngnn_cosine_hist_workspace_bytes(n, f, bins, groups)), 256), dtype=torch.uint8,
+                     device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sngnn_cosine_hist(x.data_ptr(), n, f, _lib.ptr(y32), edges.data_ptr(), bins, counts.data_ptr(),
+                                   stats.data_ptr(), ws.data_ptr(), _stream(x))
+    _lib.check(rc, "sngnn_cosine_hist")
+    return counts, stats
+
+
+def node_similarity_histogram(x, bins: int = 200, range=(-1.0, 1.0), y=None, clamp: bool = True):
+    """The distribution plot.py:61 draws from dense.py:144-149's ``sim`` - the histogram of all N (N - 1)
+    off-diagonal cosines - at any N: one scan of ``x`` by ``sngnn_cosine_hist`` (csrc/cosine_hist.hip), S is
+    never stored.  numpy's bin rule on ``edges = linspace(lo, hi, bins + 1)`` (float64, rounded to fp32): bin b
+    holds ``edges[b] <= s < edges[b + 1]``, the last bin is closed on the right.
+
+    ``y`` (optional, [N] integer labels; negative = unlabelled, counted with "different") splits the counts
+    into pairs of equal / different label.  ``clamp=True`` folds values outside ``range`` into the first / last
+    bin (``outside`` is then 0; a duplicate row's cosine may round to 1 + 1 ulp); ``clamp=False`` is numpy's
+    behaviour: they are left out of ``counts`` and reported in ``outside``.  ``range=None`` uses the data's own
+    [min, max] (one scan for them - it reads the host - and one to count).  ``mean`` equals
+    ``node_similarity_dense_large_parted(x, corrected=True)[1]``."""
+    bins = int(bins)
+    if not 1 <= bins <= HIST_MAX_BINS:
+        raise ValueError(f"bins must be in [1, {HIST_MAX_BINS}]")
+    if range is not None:
+        lo, hi = float(range[0]), float(range[1])
+        if not (lo < hi) or lo in (float("inf"), float("-inf")) or hi in (float("inf"), float("-inf")):
+            raise ValueError("range must be (lo, hi) with finite lo < hi")
+    x = _x(x)
+    n = x.size(0)
+    y32 = None
+    if y is not None:
+        y32 = y.to(device=x.device, dtype=torch.int32).contiguous()
+        if y32.dim() != 1 or y32.numel() != n:
+            raise ValueError("y must be [N]")
+
+    def make_edges(lo, hi):
+        return _hist_edges(lo, hi, bins, x.device)
+
+    if range is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("range=None reads the data's min / max on the host and cannot be captured in a "
+                               "graph: pass a fixed range")
+        _, st = _hist_scan(x, None, make_edges(-1.0, 1.0), bins)
+        lo, hi = (float(v) for v in st[:2].tolist())
+        if not lo <= hi:                       # no pairs (N <= 1): numpy's range of an empty input
+            lo, hi = 0.0, 1.0
+        if lo == hi:                           # numpy: a single value gets a bin of width 1 around it
+            lo, hi = lo - 0.5, hi + 0.5
+    edges = make_edges(lo, hi)
+    raw, stats = _hist_scan(x, y32, edges, bins)
+    counts = raw[:, 1:bins + 1].clone()
+    outside = torch.stack([raw[:, 0], raw[:, bins + 1]], dim=1)
+    if clamp:
+        counts[:, 0] += outside[:, 0]
+        counts[:, -1] += outside[:, 1]
+        outside = torch.zeros_like(outside)
+    if y32 is None:
+        counts, outside = counts[0], outside[0]
+    pairs = n * (n - 1)
+    mean = stats[2] / pairs if pairs > 0 else stats[2] * float("nan")
+    return SimilarityHistogram(counts, edges, outside, stats[0].to(torch.float32), stats[1].to(torch.float32), mean)
 
 
 def linked_node_similarity_dense_small(x, edge_index):
