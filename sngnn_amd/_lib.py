@@ -9,6 +9,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import torch
+from torch import Tensor
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SNGNN_LIB_PATH: an experimental build of the same library for an A/B measurement; the product is the in-tree file)
 LIB_PATH = os.environ.get("SNGNN_LIB_PATH") or os.path.join(_HERE, "libsngnn_hip.so")
@@ -116,6 +119,9 @@ SIGNATURES = {
     "sngnn_replica_blend_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# the one status entry that ends in a c_void_p which is NOT the stream (a host buffer): it stays on ``check``; every
+# other c_int entry whose last argument is a c_void_p takes the stream there and is entered through ``call``
+STREAMLESS = ("sngnn_graph_copy_array",)
 
 
 class Epilogue(C.Structure):
@@ -128,6 +134,7 @@ class Epilogue(C.Structure):
 
 
 _lib = None
+_entries = {}          # name -> bound function of every entry ``call`` may enter (filled by load)
 
 
 class SngnnError(RuntimeError):
@@ -147,6 +154,8 @@ def load():
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
+            if res is _i32 and args and args[-1] is _vp and name not in STREAMLESS:
+                _entries[name] = fn
         _lib = lib
     return _lib
 
@@ -161,3 +170,60 @@ def check(rc: int, what: str) -> None:
 def ptr(t):
     """Device/host pointer of a tensor (or None)."""
     return None if t is None else t.data_ptr()
+
+
+_guard, _current_stream = torch.cuda.device, torch.cuda.current_stream
+
+
+def _ordinal(device):
+    """``device``'s index where it has one: handed an int, torch's device guard and stream lookup skip their
+    parsing of a ``torch.device`` (about 2 us of host time each, per call)."""
+    idx = getattr(device, "index", None)
+    return device if idx is None else idx
+
+
+def stream(device) -> int:
+    return _current_stream(_ordinal(device)).cuda_stream
+
+
+def _entry(name):
+    load()          # (fills _entries on first use)
+    if name not in _entries:
+        raise SngnnError(f"{name} is not a status entry that takes the stream last")
+    return _entries[name]
+
+
+def call(name, device, *args):
+    """Enter the stream-taking, status-returning C entry ``name`` on ``device``'s current stream: tensors go in
+    as their ``data_ptr()`` (and must be contiguous - the kernels index dense rows), None and everything else
+    (ints, floats, ``ctypes.byref``, graph handles) as they are; the stream is appended.  Only enqueues."""
+    try:
+        fn = _entries[name]
+    except KeyError:
+        fn = _entry(name)
+    ptrs = []
+    add = ptrs.append
+    for a in args:
+        if type(a) is Tensor or isinstance(a, Tensor):
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: argument {len(ptrs) + 1} must be a contiguous tensor, got shape "
+                                 f"{tuple(a.shape)} with strides {a.stride()}")
+            a = a.data_ptr()
+        add(a)
+    idx = _ordinal(device)
+    with _guard(idx):
+        rc = fn(*ptrs, _current_stream(idx).cuda_stream)
+    if rc != 0:
+        check(rc, name)
+
+
+_ws_cache = {}
+
+
+def workspace(key, nbytes, device):
+    """Grow-only scratch per (purpose, device) for the entries whose ``*_workspace_bytes`` depends on the call."""
+    ws = _ws_cache.get((key, str(device)))
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        _ws_cache[(key, str(device))] = ws
+    return ws

@@ -39,12 +39,11 @@ class Graph:
         # remove_loops: False/True as in the SNConv layers, or LOOPS_REPLACE (AGNNConv's order)
         self.add_loops, self.remove_loops = bool(add_loops), int(remove_loops)
         handle = C.c_void_p()
+        r0, r1 = (0, int(num_nodes)) if row_range is None else map(int, row_range)
+        # (not through _lib.call: the stream is not this entry's last argument - the handle comes after it)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            r0, r1 = (0, int(num_nodes)) if row_range is None else map(int, row_range)
-            rc = lib.sngnn_graph_create_partition(ei.data_ptr(), ei.size(1), int(num_nodes),
-                                                  r0, r1, int(add_loops), int(remove_loops),
-                                                  stream, C.byref(handle))
+            rc = lib.sngnn_graph_create_partition(ei.data_ptr(), ei.size(1), int(num_nodes), r0, r1, int(add_loops),
+                                                  int(remove_loops), _lib.stream(self.device), C.byref(handle))
         _lib.check(rc, "sngnn_graph_create_partition")
         self._h = handle
         self.num_nodes = int(lib.sngnn_graph_num_nodes(handle))            # owned rows
@@ -65,7 +64,7 @@ class Graph:
         calls on the same graph from different streams never share scratch (the entry
         points are re-entrant per stream).  Allocated on first use: ``GraphedEpoch`` runs an
         eager pass on the very stream it then captures on, so the capture finds its buffers."""
-        key = (channels, torch.cuda.current_stream(self.device).cuda_stream)
+        key = (channels, _lib.stream(self.device))
         ws = self._ws.get(key)
         if ws is None:
             nbytes = int(_lib.load().sngnn_graph_workspace_bytes(self._h, channels))
@@ -77,7 +76,7 @@ class Graph:
         """Scratch of the classification head inside this graph's forward (``sngnn_epilogue_t.head_workspace``):
         one buffer per stream, owned by the graph like :meth:`workspace` - a captured epoch that holds the
         graph holds the buffer its launches point into."""
-        key = ("head", torch.cuda.current_stream(self.device).cuda_stream)
+        key = ("head", _lib.stream(self.device))
         ws = self._ws.get(key)
         if ws is None:
             nbytes = int(_lib.load().sngnn_agg_head_workspace_bytes(self._h))
@@ -91,6 +90,7 @@ class Graph:
         n = {0: self.num_nodes + 1, 3: self.num_total_nodes + 1,
              5: self.num_nodes}.get(which, self.num_edges)
         out = np.empty(n, dtype=np.int32)
+        # (not through _lib.call: a blocking copy to host memory, the entry takes no stream)
         _lib.check(_lib.load().sngnn_graph_copy_array(self._h, which, out.ctypes.data),
                    "sngnn_graph_copy_array")
         return out

@@ -7,6 +7,7 @@ loop over torch_scatter.scatter_max and the mean aggregation
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -34,8 +35,9 @@ def _check_rows(t: torch.Tensor, n: int, what: str, half: bool = False) -> torch
     return t.contiguous()
 
 
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+def _k(top_k: Optional[int]) -> int:
+    """The C ABI's top_k: -1 = no selection."""
+    return -1 if top_k is None else int(top_k)
 
 
 def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: float, *,
@@ -44,11 +46,10 @@ def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: 
     unless requested.  ``top_k=None`` is SNConv (no selection).  A float16 / bfloat16 ``h`` takes
     the half path: ``out`` in h's dtype (the fp32 operator on h.float(), scored on the fly, its
     rows rounded once), everything else fp32."""
-    lib = _lib.load()
     n = graph.num_nodes
     h = _check_rows(h, graph.num_total_nodes, "h", half=True)
     c = h.size(1)
-    k = -1 if top_k is None else int(top_k)
+    k = _k(top_k)
     if top_k is not None and k < 0:
         raise ValueError("top_k must be >= 0")
     out = torch.empty((n, c), dtype=h.dtype, device=h.device)
@@ -63,30 +64,20 @@ def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: 
         sel_w = torch.empty((n, k), dtype=torch.float32, device=h.device)
     ws = graph.workspace(c)
     if h.dtype in HALF_DTYPES:
-        with torch.cuda.device(h.device):
-            rc = lib.sngnn_agg_forward_half(graph.handle, h.data_ptr(), HALF_DTYPES[h.dtype], c, k, float(thr),
-                                            out.data_ptr(), _lib.ptr(wsel), _lib.ptr(inv), _lib.ptr(sel_src),
-                                            _lib.ptr(sel_w), ws.data_ptr(), _stream(h.device))
-        _lib.check(rc, "sngnn_agg_forward_half")
-        return out, wsel, inv, sel_src, sel_w
-    with torch.cuda.device(h.device):
-        rc = lib.sngnn_agg_forward(graph.handle, h.data_ptr(), c, k, float(thr), out.data_ptr(),
-                                   _lib.ptr(wsel), _lib.ptr(inv), _lib.ptr(sel_src),
-                                   _lib.ptr(sel_w), ws.data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_agg_forward")
+        _lib.call("sngnn_agg_forward_half", h.device, graph.handle, h, HALF_DTYPES[h.dtype], c, k, float(thr),
+                  out, wsel, inv, sel_src, sel_w, ws)
+    else:
+        _lib.call("sngnn_agg_forward", h.device, graph.handle, h, c, k, float(thr), out, wsel, inv, sel_src, sel_w, ws)
     return out, wsel, inv, sel_src, sel_w
 
 
 def normalize_rows(h: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``sngnn_normalize_rows``: F.normalize(h, p=2, dim=-1) (models.py:122,238,325) with IEEE
+    """``sngnn_normalize_rows_filter`` without filter rows: F.normalize(h, p=2, dim=-1) (models.py:122,238,325) with IEEE
     square root and division.  Returns (unit rows [rows, C], clamped norms [rows])."""
     h = _check_rows(h, h.size(0), "h")
     n = torch.empty_like(h)
     nrm = torch.empty(h.size(0), dtype=torch.float32, device=h.device)
-    with torch.cuda.device(h.device):
-        rc = _lib.load().sngnn_normalize_rows(h.data_ptr(), h.size(0), h.size(1), n.data_ptr(),
-                                              nrm.data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_normalize_rows")
+    normalize_rows_into(h, n, nrm, None)
     return n, nrm
 
 
@@ -102,17 +93,13 @@ def normalize_rows_filter(h: torch.Tensor):
     nrm = torch.empty(h.size(0), dtype=torch.float32, device=h.device)
     fb = filter_row_bytes(h.size(1))
     filt = torch.empty((h.size(0), fb), dtype=torch.uint8, device=h.device) if fb else None
-    with torch.cuda.device(h.device):
-        rc = _lib.load().sngnn_normalize_rows_filter(h.data_ptr(), h.size(0), h.size(1), n.data_ptr(),
-                                                     nrm.data_ptr(), _lib.ptr(filt), _stream(h.device))
-    _lib.check(rc, "sngnn_normalize_rows_filter")
+    normalize_rows_into(h, n, nrm, filt)
     return n, nrm, filt
 
 
 def filter_wanted(graph: Graph, c: int, top_k: Optional[int], thr: float) -> bool:
     """``sngnn_filter_wanted``: whether a forward with these arguments uses filter rows."""
-    k = -1 if top_k is None else int(top_k)
-    return bool(_lib.load().sngnn_filter_wanted(graph.handle, int(c), k, float(thr)))
+    return bool(_lib.load().sngnn_filter_wanted(graph.handle, int(c), _k(top_k), float(thr)))
 
 
 def normalize_rows_into(h: torch.Tensor, n: torch.Tensor, nrm: torch.Tensor, filt: Optional[torch.Tensor]) -> None:
@@ -125,10 +112,7 @@ def normalize_rows_into(h: torch.Tensor, n: torch.Tensor, nrm: torch.Tensor, fil
         raise ValueError("normalize_rows_into needs contiguous row blocks")
     if n.shape != h.shape or nrm.numel() != rows or (filt is not None and filt.size(0) != rows):
         raise ValueError("normalize_rows_into: buffer shapes do not match h")
-    with torch.cuda.device(h.device):
-        rc = _lib.load().sngnn_normalize_rows_filter(h.data_ptr(), rows, c, n.data_ptr(), nrm.data_ptr(),
-                                                     _lib.ptr(filt), _stream(h.device))
-    _lib.check(rc, "sngnn_normalize_rows_filter")
+    _lib.call("sngnn_normalize_rows_filter", h.device, h, rows, c, n, nrm, filt)
 
 
 def aggregate_forward_rows(graph: Graph, n: torch.Tensor, nrm: torch.Tensor, filt: Optional[torch.Tensor],
@@ -140,17 +124,12 @@ def aggregate_forward_rows(graph: Graph, n: torch.Tensor, nrm: torch.Tensor, fil
     ``nrm=None``: ``n`` holds the RAW rows h and the call scores on the fly (what
     ``sngnn_agg_forward`` does by itself when nothing is selected, top_k None)."""
     c = n.size(1)
-    k = -1 if top_k is None else int(top_k)
     if row_flag.dtype != torch.uint8 or row_flag.numel() != graph.num_nodes or not row_flag.is_contiguous():
         raise ValueError("row_flag must be a contiguous uint8 tensor with one entry per owned row")
     if n.size(0) != graph.num_total_nodes or out.shape != (graph.num_nodes, c):
         raise ValueError("n must hold one row per feature-table row and out one per owned row")
-    ws = graph.workspace(c)
-    with torch.cuda.device(n.device):
-        rc = _lib.load().sngnn_agg_forward_rows(graph.handle, n.data_ptr(), _lib.ptr(nrm), _lib.ptr(filt), c, k,
-                                                float(thr), row_flag.data_ptr(), int(want), out.data_ptr(),
-                                                _lib.ptr(wsel), _lib.ptr(inv), ws.data_ptr(), _stream(n.device))
-    _lib.check(rc, "sngnn_agg_forward_rows")
+    _lib.call("sngnn_agg_forward_rows", n.device, graph.handle, n, nrm, filt, c, _k(top_k), float(thr), row_flag,
+              int(want), out, wsel, inv, graph.workspace(c))
 
 
 def aggregate_forward_normalized(graph: Graph, n: torch.Tensor, nrm: torch.Tensor,
@@ -158,25 +137,33 @@ def aggregate_forward_normalized(graph: Graph, n: torch.Tensor, nrm: torch.Tenso
                                  filt: Optional[torch.Tensor] = None):
     """``sngnn_agg_forward_prepared``: the aggregation on unit rows + norms (+ filter rows)
     that the caller already holds.  Returns (out, sel_src, sel_w)."""
-    lib = _lib.load()
     n = _check_rows(n, graph.num_total_nodes, "n")
     if nrm.dtype != torch.float32 or nrm.numel() != graph.num_total_nodes or not nrm.is_cuda:
         raise ValueError("nrm must be a float32 GPU tensor with one entry per feature row")
-    nrm = nrm.contiguous()
-    c = n.size(1)
-    k = -1 if top_k is None else int(top_k)
-    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=n.device)
-    sel_src = sel_w = None
-    if want_selection:
-        sel_src = torch.empty((graph.num_nodes, k), dtype=torch.int32, device=n.device)
-        sel_w = torch.empty((graph.num_nodes, k), dtype=torch.float32, device=n.device)
-    ws = graph.workspace(c)
-    with torch.cuda.device(n.device):
-        rc = lib.sngnn_agg_forward_prepared(graph.handle, n.data_ptr(), nrm.data_ptr(), _lib.ptr(filt), c, k,
-                                            float(thr), out.data_ptr(), None, None, _lib.ptr(sel_src),
-                                            _lib.ptr(sel_w), ws.data_ptr(), _stream(n.device))
-    _lib.check(rc, "sngnn_agg_forward_prepared")
+    out, _, sel_src, sel_w = _prepared(graph, n, nrm.contiguous(), filt, top_k, thr, False, want_selection)
     return out, sel_src, sel_w
+
+
+def _prepared(graph: Graph, n, nrm, filt, top_k, thr, need_grad: bool, want_selection: bool):
+    """The one caller of ``sngnn_agg_forward_prepared``: returns (out, wsel, sel_src, sel_w), ``wsel`` only with
+    ``need_grad`` and the selection only with ``want_selection``."""
+    rows, c, k = graph.num_nodes, n.size(1), _k(top_k)
+    out = torch.empty((rows, c), dtype=torch.float32, device=n.device)
+    wsel = inv = sel_src = sel_w = None
+    if need_grad:
+        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=n.device)
+        inv = torch.empty(rows, dtype=torch.float32, device=n.device)
+    if want_selection:
+        sel_src = torch.empty((rows, k), dtype=torch.int32, device=n.device)
+        sel_w = torch.empty((rows, k), dtype=torch.float32, device=n.device)
+    _lib.call("sngnn_agg_forward_prepared", n.device, graph.handle, n, nrm, filt, c, k, float(thr), out, wsel, inv,
+              sel_src, sel_w, graph.workspace(c))
+    return out, wsel, sel_src, sel_w
+
+
+def _forward_prepared(graph: Graph, unit: "UnitRows", top_k, thr, need_grad):
+    """The training form on the unit rows ``lin``'s epilogue left (``UnitRows``): (out, wsel)."""
+    return _prepared(graph, unit.n, unit.nrm, unit.filt, top_k, thr, need_grad, False)[:2]
 
 
 def aggregate_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
@@ -185,7 +172,6 @@ def aggregate_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
     take every node in one launch) or None when unknown / nothing was selected.  A float16 /
     bfloat16 ``h`` (and ``grad_out`` of the same dtype) takes the half path: ``grad_h`` in that dtype,
     the fp32 backward on the widened rows rounded once."""
-    lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h", half=True)
     grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out", half=True)
     c = h.size(1)
@@ -194,20 +180,12 @@ def aggregate_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
     if h.dtype in HALF_DTYPES:
         if grad_out.dtype != h.dtype:
             raise ValueError(f"grad_out must have h's dtype {h.dtype}, got {grad_out.dtype}")
-        with torch.cuda.device(h.device):
-            rc = lib.sngnn_agg_backward_half(graph.handle, h.data_ptr(), HALF_DTYPES[h.dtype], c,
-                                             grad_out.data_ptr(), wsel.data_ptr(),
-                                             -1 if top_k is None else int(top_k), grad_h.data_ptr(),
-                                             ws.data_ptr(), _stream(h.device))
-        _lib.check(rc, "sngnn_agg_backward_half")
+        _lib.call("sngnn_agg_backward_half", h.device, graph.handle, h, HALF_DTYPES[h.dtype], c, grad_out, wsel,
+                  _k(top_k), grad_h, ws)
         return grad_h
     if grad_out.dtype != torch.float32:
         raise ValueError("grad_out must be float32 (the reference path is fp32 only)")
-    with torch.cuda.device(h.device):
-        rc = lib.sngnn_agg_backward_topk(graph.handle, h.data_ptr(), c, grad_out.data_ptr(),
-                                         wsel.data_ptr(), -1 if top_k is None else int(top_k),
-                                         grad_h.data_ptr(), ws.data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_agg_backward_topk")
+    _lib.call("sngnn_agg_backward_topk", h.device, graph.handle, h, c, grad_out, wsel, _k(top_k), grad_h, ws)
     return grad_h
 
 
@@ -222,15 +200,12 @@ def kept_bits_supported(graph: Graph, top_k: Optional[int], channels: int = 64) 
 def aggregate_backward_bits(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor, kept_bits: torch.Tensor,
                             top_k: int) -> torch.Tensor:
     """``sngnn_agg_backward_bits``: the backward from the kept bits the forward wrote."""
-    lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h")
     grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out")
     c = h.size(1)
     grad_h = torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        rc = lib.sngnn_agg_backward_bits(graph.handle, h.data_ptr(), c, grad_out.data_ptr(), kept_bits.data_ptr(),
-                                         int(top_k), grad_h.data_ptr(), graph.workspace(c).data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_agg_backward_bits")
+    _lib.call("sngnn_agg_backward_bits", h.device, graph.handle, h, c, grad_out, kept_bits, int(top_k), grad_h,
+              graph.workspace(c))
     return grad_h
 
 
@@ -314,7 +289,7 @@ class HeadEpilogue:
 
 def head_supported(graph: Graph, channels: int, top_k: Optional[int]) -> bool:
     """``sngnn_agg_head_supported``: whether a forward on this graph at this width can take the head."""
-    return bool(_lib.load().sngnn_agg_head_supported(graph.handle, int(channels), -1 if top_k is None else int(top_k)))
+    return bool(_lib.load().sngnn_agg_head_supported(graph.handle, int(channels), _k(top_k)))
 
 
 class _Aggregate(torch.autograd.Function):
@@ -377,10 +352,7 @@ class _Aggregate(torch.autograd.Function):
             else:
                 g = grad_out.contiguous()
                 grad_out = torch.empty_like(g)
-                with torch.cuda.device(g.device):
-                    rc = _lib.load().sngnn_epilogue_backward(g.data_ptr(), out.data_ptr(), float(epi.scale), g.numel(),
-                                                             grad_out.data_ptr(), _stream(g.device))
-                _lib.check(rc, "sngnn_epilogue_backward")
+                _lib.call("sngnn_epilogue_backward", g.device, g, out, float(epi.scale), g.numel(), grad_out)
             if ctx.bias_grad:
                 grad_bias = grad_out.sum(dim=0)
         if epi is None and ctx.bias_grad:          # (the head epilogue added the conv's bias)
@@ -406,25 +378,6 @@ class UnitRows:
         self.n = self.nrm = self.filt = None
 
 
-def _forward_prepared(graph: Graph, unit: "UnitRows", top_k, thr, need_grad):
-    lib = _lib.load()
-    n = unit.n
-    c = n.size(1)
-    k = -1 if top_k is None else int(top_k)
-    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=n.device)
-    wsel = inv = None
-    if need_grad:
-        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=n.device)
-        inv = torch.empty(graph.num_nodes, dtype=torch.float32, device=n.device)
-    ws = graph.workspace(c)
-    with torch.cuda.device(n.device):
-        rc = lib.sngnn_agg_forward_prepared(graph.handle, n.data_ptr(), unit.nrm.data_ptr(), _lib.ptr(unit.filt), c, k,
-                                            float(thr), out.data_ptr(), _lib.ptr(wsel), _lib.ptr(inv), None, None,
-                                            ws.data_ptr(), _stream(n.device))
-    _lib.check(rc, "sngnn_agg_forward_prepared")
-    return out, wsel
-
-
 def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optional["HiddenEpilogue"], bias,
                       bits: bool = False, head: Optional["HeadEpilogue"] = None):
     """``sngnn_agg_forward_epilogue`` / ``_prepared_epilogue``: the forward whose stores apply
@@ -435,7 +388,6 @@ def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optiona
     lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h")
     n, c = graph.num_nodes, h.size(1)
-    k = -1 if top_k is None else int(top_k)
     out = torch.empty((n, c), dtype=torch.float32, device=h.device)
     wsel = inv = keep = kbits = None
     if need_grad and bits:
@@ -466,24 +418,19 @@ def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optiona
     if head is not None:
         if head.y.numel() != n or head.sel.numel() != n or head.y.device != h.device or head.sel.device != h.device:
             raise ValueError("head: y and sel must hold one entry per target row, on h's device")
+        if not (head.y.is_contiguous() and head.sel.is_contiguous() and head.metrics.is_contiguous()):
+            raise ValueError("head: y, sel and metrics must be contiguous (they go in as addresses)")
         hws = graph.head_workspace()
         st.head_y, st.head_sel = head.y.data_ptr(), head.sel.data_ptr()
         st.head_sets, st.head_out_mode = head.sets, head.out_mode
         st.head_n_a, st.head_n_b = head.n_a, head.n_b
         st.head_metrics, st.head_workspace = head.metrics.data_ptr(), hws.data_ptr()
-    ws = graph.workspace(c)
-    import ctypes
-    with torch.cuda.device(h.device):
-        if unit is not None and unit.n is not None:
-            rc = lib.sngnn_agg_forward_prepared_epilogue(graph.handle, unit.n.data_ptr(), unit.nrm.data_ptr(),
-                                                         _lib.ptr(unit.filt), c, k, float(thr), ctypes.byref(st),
-                                                         out.data_ptr(), _lib.ptr(wsel), _lib.ptr(inv), ws.data_ptr(),
-                                                         _stream(h.device))
-        else:
-            rc = lib.sngnn_agg_forward_epilogue(graph.handle, h.data_ptr(), c, k, float(thr), ctypes.byref(st),
-                                                out.data_ptr(), _lib.ptr(wsel), _lib.ptr(inv), ws.data_ptr(),
-                                                _stream(h.device))
-    _lib.check(rc, "sngnn_agg_forward_epilogue")
+    k, thr, epi_ref, ws = _k(top_k), float(thr), ctypes.byref(st), graph.workspace(c)
+    if unit is not None and unit.n is not None:
+        _lib.call("sngnn_agg_forward_prepared_epilogue", h.device, graph.handle, unit.n, unit.nrm, unit.filt, c, k, thr,
+                  epi_ref, out, wsel, inv, ws)
+    else:
+        _lib.call("sngnn_agg_forward_epilogue", h.device, graph.handle, h, c, k, thr, epi_ref, out, wsel, inv, ws)
     return out, (kbits if kbits is not None else wsel)
 
 
@@ -504,31 +451,22 @@ def aggregate(h: torch.Tensor, graph: Graph, top_k: Optional[int], thr: float,
 def attention_forward(graph: Graph, h: torch.Tensor, save_for_backward: bool = True):
     """``sngnn_attn_forward``: softmax-of-cosine attention (AGNNConv after ``lin``,
     models.py:396-405).  Returns (out [N, C], alpha [E'] in CSR order or None)."""
-    lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h")
     c = h.size(1)
     out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=h.device)
     alpha = (torch.empty(graph.num_edges, dtype=torch.float32, device=h.device)
              if save_for_backward else None)
-    with torch.cuda.device(h.device):
-        rc = lib.sngnn_attn_forward(graph.handle, h.data_ptr(), c, out.data_ptr(), _lib.ptr(alpha),
-                                    graph.workspace(c).data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_attn_forward")
+    _lib.call("sngnn_attn_forward", h.device, graph.handle, h, c, out, alpha, graph.workspace(c))
     return out, alpha
 
 
 def attention_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
                        alpha: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h")
     grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out")
     c = h.size(1)
     grad_h = torch.empty_like(h)
-    with torch.cuda.device(h.device):
-        rc = lib.sngnn_attn_backward(graph.handle, h.data_ptr(), c, grad_out.data_ptr(),
-                                     alpha.data_ptr(), grad_h.data_ptr(),
-                                     graph.workspace(c).data_ptr(), _stream(h.device))
-    _lib.check(rc, "sngnn_attn_backward")
+    _lib.call("sngnn_attn_backward", h.device, graph.handle, h, c, grad_out, alpha, grad_h, graph.workspace(c))
     return grad_h
 
 
@@ -564,7 +502,6 @@ class _SignedPropagate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, wh, coef, c2, graph):
-        lib = _lib.load()
         wh = _check_rows(wh, graph.num_total_nodes, "wh")
         c = wh.size(1)
         if coef.dtype != torch.float32 or coef.numel() != graph.num_edges or not coef.is_cuda:
@@ -574,11 +511,7 @@ class _SignedPropagate(torch.autograd.Function):
         coef, c2 = coef.contiguous(), c2.contiguous()
         out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=wh.device)
         s = torch.empty(graph.num_edges, dtype=torch.float32, device=wh.device)
-        with torch.cuda.device(wh.device):
-            rc = lib.sngnn_signed_forward(graph.handle, wh.data_ptr(), c, coef.data_ptr(), c2.data_ptr(),
-                                          out.data_ptr(), s.data_ptr(), graph.workspace(c).data_ptr(),
-                                          _stream(wh.device))
-        _lib.check(rc, "sngnn_signed_forward")
+        _lib.call("sngnn_signed_forward", wh.device, graph.handle, wh, c, coef, c2, out, s, graph.workspace(c))
         ctx.graph = graph
         ctx.save_for_backward(wh, coef, c2, s)
         return out
@@ -587,16 +520,12 @@ class _SignedPropagate(torch.autograd.Function):
     def backward(ctx, g):
         wh, coef, c2, s = ctx.saved_tensors
         graph = ctx.graph
-        lib = _lib.load()
         g = _check_rows(g.contiguous(), graph.num_nodes, "grad_out")
         c = wh.size(1)
         grad_wh = torch.empty_like(wh)
         u = torch.empty_like(s)
-        with torch.cuda.device(wh.device):
-            rc = lib.sngnn_signed_backward(graph.handle, wh.data_ptr(), c, g.data_ptr(), coef.data_ptr(),
-                                           s.data_ptr(), c2.data_ptr(), grad_wh.data_ptr(), u.data_ptr(),
-                                           graph.workspace(c).data_ptr(), _stream(wh.device))
-        _lib.check(rc, "sngnn_signed_backward")
+        _lib.call("sngnn_signed_backward", wh.device, graph.handle, wh, c, g, coef, s, c2, grad_wh, u,
+                  graph.workspace(c))
         pos, neg = s > 0, s < 0
         zero = torch.zeros((), dtype=torch.float32, device=s.device)
         kappa = torch.where(pos, c2[0], torch.where(neg, c2[1], zero))
@@ -620,17 +549,13 @@ class _WeightedPropagate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_csr, graph, aux):
-        lib = _lib.load()
         x = _check_rows(x, graph.num_total_nodes, "x")
         c = x.size(1)
         if w_csr.dtype != torch.float32 or w_csr.numel() != graph.num_edges or not w_csr.is_cuda:
             raise ValueError("w_csr must be a float32 GPU tensor with one entry per edge of the graph")
         w_csr = w_csr.contiguous()
         out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = lib.sngnn_weighted_gather_sum_rows(graph.handle, x.data_ptr(), w_csr.data_ptr(), c, out.data_ptr(),
-                                                    graph.workspace(c).data_ptr(), _stream(x.device))
-        _lib.check(rc, "sngnn_weighted_gather_sum_rows")
+        _lib.call("sngnn_weighted_gather_sum_rows", x.device, graph.handle, x, w_csr, c, out, graph.workspace(c))
         ctx.graph, ctx.aux = graph, aux
         ctx.save_for_backward(x, w_csr)
         return out
@@ -640,22 +565,16 @@ class _WeightedPropagate(torch.autograd.Function):
         x, w_csr = ctx.saved_tensors
         graph = ctx.graph
         csc_eid, tgt, src = ctx.aux
-        lib = _lib.load()
         g = _check_rows(g.contiguous(), graph.num_nodes, "grad_out")
         c = x.size(1)
         gx = gw = None
-        with torch.cuda.device(x.device):
-            if ctx.needs_input_grad[0]:
-                gx = torch.empty_like(x)
-                w_csc = w_csr.index_select(0, csc_eid)
-                rc = lib.sngnn_weighted_scatter_sum_rows(graph.handle, g.data_ptr(), w_csc.data_ptr(), c, gx.data_ptr(),
-                                                         graph.workspace(c).data_ptr(), _stream(x.device))
-                _lib.check(rc, "sngnn_weighted_scatter_sum_rows")
-            if ctx.needs_input_grad[1]:
-                gw = torch.empty_like(w_csr)
-                rc = lib.sngnn_pair_dot_rows(g.data_ptr(), tgt.data_ptr(), x.data_ptr(), src.data_ptr(), w_csr.numel(), c,
-                                             gw.data_ptr(), _stream(x.device))
-                _lib.check(rc, "sngnn_pair_dot_rows")
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            w_csc = w_csr.index_select(0, csc_eid)
+            _lib.call("sngnn_weighted_scatter_sum_rows", x.device, graph.handle, g, w_csc, c, gx, graph.workspace(c))
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(w_csr)
+            _lib.call("sngnn_pair_dot_rows", x.device, g, tgt, x, src, w_csr.numel(), c, gw)
         return gx, gw, None, None
 
 
@@ -665,28 +584,18 @@ def weighted_propagate(x: torch.Tensor, w_csr: torch.Tensor, graph: Graph, aux) 
 
 
 def adj_linear_forward(graph: Graph, wt: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    lib = _lib.load()
     wt = _check_rows(wt, graph.num_nodes, "wt")
     c = wt.size(1)
     out0 = torch.empty_like(wt)
     b = None if bias is None else bias.contiguous()
-    with torch.cuda.device(wt.device):
-        rc = lib.sngnn_adj_linear_forward(graph.handle, wt.data_ptr(), _lib.ptr(b), c,
-                                          out0.data_ptr(), graph.workspace(c).data_ptr(),
-                                          _stream(wt.device))
-    _lib.check(rc, "sngnn_adj_linear_forward")
+    _lib.call("sngnn_adj_linear_forward", wt.device, graph.handle, wt, b, c, out0, graph.workspace(c))
     return out0
 
 
 def adj_linear_backward(graph: Graph, g0: torch.Tensor) -> torch.Tensor:
-    lib = _lib.load()
     g0 = _check_rows(g0, graph.num_nodes, "g0")
     dwt = torch.empty_like(g0)
-    with torch.cuda.device(g0.device):
-        rc = lib.sngnn_adj_linear_backward(graph.handle, g0.data_ptr(), g0.size(1),
-                                           dwt.data_ptr(), graph.workspace(g0.size(1)).data_ptr(),
-                                           _stream(g0.device))
-    _lib.check(rc, "sngnn_adj_linear_backward")
+    _lib.call("sngnn_adj_linear_backward", g0.device, graph.handle, g0, g0.size(1), dwt, graph.workspace(g0.size(1)))
     return dwt
 
 
@@ -716,6 +625,27 @@ def adj_linear(weight: torch.Tensor, bias: Optional[torch.Tensor], graph: Graph)
     return _AdjLinear.apply(weight, bias, graph)
 
 
+def _gather_sum_rows(ctx, table, bias, graph):
+    """Forward of the two gather-sums below: ``out[i] = bias + sum_{q in row i} table[col_q]``."""
+    c = table.size(1)
+    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=table.device)
+    b = None if bias is None else bias.contiguous()
+    _lib.call("sngnn_gather_sum_rows", table.device, graph.handle, table, b, c, out, graph.workspace(c))
+    ctx.graph = graph
+    ctx.has_bias = bias is not None
+    return out
+
+
+def _scatter_sum_rows(ctx, g0):
+    """Their backward: (the [N_total, C] gradient of the table - the transpose gather - and the bias')."""
+    g0 = g0.contiguous()
+    gr = ctx.graph
+    c = g0.size(1)
+    dtab = torch.empty((gr.num_total_nodes, c), dtype=torch.float32, device=g0.device)
+    _lib.call("sngnn_scatter_sum_rows", g0.device, gr.handle, g0, c, dtab, gr.workspace(c))
+    return dtab, (g0.sum(dim=0) if ctx.has_bias else None)
+
+
 class _AdjLinearPartition(torch.autograd.Function):
     """The adjacency branch of one rank of a node-range partition.  ``graph_out`` is the
     partition of the FLIPPED edge list (its owned rows are the rank's own source
@@ -726,37 +656,18 @@ class _AdjLinearPartition(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, weight, bias, graph_out):
-        lib = _lib.load()
         wt = weight.t()
         if not wt.is_contiguous():
             wt = wt.contiguous()
-        c = wt.size(1)
         if wt.size(0) != graph_out.num_total_nodes:
             raise ValueError("w.weight must cover all N_total nodes")
         if graph_out.src_min != 0 and graph_out.num_edges > 0:
             raise ValueError("the partitioned adjacency branch needs a graph whose lowest target id is 0")
-        out = torch.empty((graph_out.num_nodes, c), dtype=torch.float32, device=wt.device)
-        b = None if bias is None else bias.contiguous()
-        with torch.cuda.device(wt.device):
-            rc = lib.sngnn_gather_sum_rows(graph_out.handle, wt.data_ptr(), _lib.ptr(b), c, out.data_ptr(),
-                                           graph_out.workspace(c).data_ptr(), _stream(wt.device))
-        _lib.check(rc, "sngnn_gather_sum_rows")
-        ctx.graph = graph_out
-        ctx.has_bias = bias is not None
-        return out
+        return _gather_sum_rows(ctx, wt, bias, graph_out)
 
     @staticmethod
     def backward(ctx, g0):
-        lib = _lib.load()
-        g0 = g0.contiguous()
-        gr = ctx.graph
-        c = g0.size(1)
-        dwt = torch.empty((gr.num_total_nodes, c), dtype=torch.float32, device=g0.device)
-        with torch.cuda.device(g0.device):
-            rc = lib.sngnn_scatter_sum_rows(gr.handle, g0.data_ptr(), c, dwt.data_ptr(),
-                                            gr.workspace(c).data_ptr(), _stream(g0.device))
-        _lib.check(rc, "sngnn_scatter_sum_rows")
-        db = g0.sum(dim=0) if ctx.has_bias else None
+        dwt, db = _scatter_sum_rows(ctx, g0)
         return dwt.t(), db, None
 
 
@@ -773,32 +684,11 @@ class _GatherSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, bias, graph):
-        lib = _lib.load()
-        table = _check_rows(table, graph.num_total_nodes, "table")
-        c = table.size(1)
-        out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=table.device)
-        b = None if bias is None else bias.contiguous()
-        with torch.cuda.device(table.device):
-            rc = lib.sngnn_gather_sum_rows(graph.handle, table.data_ptr(), _lib.ptr(b), c, out.data_ptr(),
-                                           graph.workspace(c).data_ptr(), _stream(table.device))
-        _lib.check(rc, "sngnn_gather_sum_rows")
-        ctx.graph = graph
-        ctx.has_bias = bias is not None
-        return out
+        return _gather_sum_rows(ctx, _check_rows(table, graph.num_total_nodes, "table"), bias, graph)
 
     @staticmethod
     def backward(ctx, g0):
-        lib = _lib.load()
-        g0 = g0.contiguous()
-        gr = ctx.graph
-        c = g0.size(1)
-        dtab = torch.empty((gr.num_total_nodes, c), dtype=torch.float32, device=g0.device)
-        with torch.cuda.device(g0.device):
-            rc = lib.sngnn_scatter_sum_rows(gr.handle, g0.data_ptr(), c, dtab.data_ptr(),
-                                            gr.workspace(c).data_ptr(), _stream(g0.device))
-        _lib.check(rc, "sngnn_scatter_sum_rows")
-        db = g0.sum(dim=0) if ctx.has_bias else None
-        return dtab, db, None
+        return (*_scatter_sum_rows(ctx, g0), None)
 
 
 def gather_sum(table: torch.Tensor, bias: Optional[torch.Tensor], graph: Graph) -> torch.Tensor:
@@ -808,15 +698,7 @@ def gather_sum(table: torch.Tensor, bias: Optional[torch.Tensor], graph: Graph) 
 # ---------------------------------------------------------------------------
 # Callers on either side of the aggregation
 # ---------------------------------------------------------------------------
-_ws_cache = {}
-
-
-def _workspace(key, nbytes, device):
-    ws = _ws_cache.get((key, str(device)))
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ws_cache[(key, str(device))] = ws
-    return ws
+_workspace = _lib.workspace
 
 
 class OutBuffer:
@@ -887,16 +769,9 @@ class _Linear(torch.autograd.Function):
             unit.nrm = torch.empty(n, dtype=torch.float32, device=x.device)
             fb = int(lib.sngnn_filter_row_bytes(c)) if unit.want_filter else 0
             unit.filt = torch.empty((n, fb), dtype=torch.uint8, device=x.device) if fb == 128 else None
-            with torch.cuda.device(x.device):
-                rc = lib.sngnn_linear_forward_normalized(xc.data_ptr(), wc.data_ptr(), _lib.ptr(bc), n, f, c,
-                                                         h.data_ptr(), unit.n.data_ptr(), unit.nrm.data_ptr(),
-                                                         _lib.ptr(unit.filt), _stream(x.device))
-            _lib.check(rc, "sngnn_linear_forward_normalized")
-            return h
-        with torch.cuda.device(x.device):
-            rc = lib.sngnn_linear_forward(xc.data_ptr(), wc.data_ptr(), _lib.ptr(bc), n, f, c,
-                                          h.data_ptr(), _stream(x.device))
-        _lib.check(rc, "sngnn_linear_forward")
+            _lib.call("sngnn_linear_forward_normalized", x.device, xc, wc, bc, n, f, c, h, unit.n, unit.nrm, unit.filt)
+        else:
+            _lib.call("sngnn_linear_forward", x.device, xc, wc, bc, n, f, c, h)
         return h
 
     @staticmethod
@@ -917,16 +792,11 @@ class _Linear(torch.autograd.Function):
                 # row-tile width); the row-tile widths keep their faster kernel and leave the mask
                 # to the producer's backward
                 masked = act is not None and ctx.c not in (16, 32, 64, 128) and x.is_contiguous()
-                with torch.cuda.device(g.device):
-                    if masked:
-                        rc = _lib.load().sngnn_linear_forward_masked(g.data_ptr(), wt.data_ptr(), None, n, ctx.c, fin,
-                                                                     x.data_ptr(), float(act.scale), gx.data_ptr(),
-                                                                     _stream(g.device))
-                        act.premasked = gx.data_ptr()          # (which tensor: _take_premasked checks it)
-                    else:
-                        rc = _lib.load().sngnn_linear_forward(g.data_ptr(), wt.data_ptr(), None, n, ctx.c, fin,
-                                                              gx.data_ptr(), _stream(g.device))
-                _lib.check(rc, "sngnn_linear_forward (input gradient)")
+                if masked:
+                    _lib.call("sngnn_linear_forward_masked", g.device, g, wt, None, n, ctx.c, fin, x, float(act.scale), gx)
+                    act.premasked = gx.data_ptr()          # (which tensor: _take_premasked checks it)
+                else:
+                    _lib.call("sngnn_linear_forward", g.device, g, wt, None, n, ctx.c, fin, gx)
             else:
                 gx = g[:, :ctx.c].mm(weight)         # (the padded channels carry no gradient)
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
@@ -937,10 +807,7 @@ class _Linear(torch.autograd.Function):
             gw = torch.empty((c, f), dtype=torch.float32, device=g.device)
             gb = torch.empty(c, dtype=torch.float32, device=g.device) if ctx.has_bias else None
             ws = _workspace("wgrad", lib.sngnn_linear_wgrad_workspace_bytes(n, c, f), g.device)
-            with torch.cuda.device(g.device):
-                rc = lib.sngnn_linear_wgrad(g.data_ptr(), xc.data_ptr(), n, c, f, gw.data_ptr(),
-                                            _lib.ptr(gb), ws.data_ptr(), _stream(g.device))
-            _lib.check(rc, "sngnn_linear_wgrad")
+            _lib.call("sngnn_linear_wgrad", g.device, g, xc, n, c, f, gw, gb, ws)
             gw = gw[:ctx.c]
             gb = None if gb is None else gb[:ctx.c]
         return gx, gw, gb, None, None, None, None
@@ -961,24 +828,16 @@ class _Blend(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out0, out1, beta, epi=None):
-        lib = _lib.load()
         out = torch.empty_like(out0)
         ctx.epi = epi
-        with torch.cuda.device(out0.device):
-            if epi is None:
-                rc = lib.sngnn_blend_forward(out0.data_ptr(), out1.data_ptr(), beta.data_ptr(), out0.numel(),
-                                             out.data_ptr(), _stream(out0.device))
-            else:
-                import ctypes
-                epi.scale = 1.0 / (1.0 - epi.p) if epi.drops else 1.0
-                seed = epi.seed if epi.drops else None
-                st = _lib.Epilogue(None, None, float(epi.scale), int(epi.relu), _lib.ptr(seed), float(epi.p), None)
-                rc = lib.sngnn_blend_forward_epilogue(out0.data_ptr(), out1.data_ptr(), beta.data_ptr(), out0.numel(),
-                                                      ctypes.byref(st), out.data_ptr(), _stream(out0.device))
-        _lib.check(rc, "sngnn_blend_forward")
         if epi is None:
+            _lib.call("sngnn_blend_forward", out0.device, out0, out1, beta, out0.numel(), out)
             ctx.save_for_backward(out0, out1, beta)
         else:
+            epi.scale = 1.0 / (1.0 - epi.p) if epi.drops else 1.0
+            seed = epi.seed if epi.drops else None
+            st = _lib.Epilogue(None, None, float(epi.scale), int(epi.relu), _lib.ptr(seed), float(epi.p), None)
+            _lib.call("sngnn_blend_forward_epilogue", out0.device, out0, out1, beta, out0.numel(), ctypes.byref(st), out)
             ctx.save_for_backward(out0, out1, beta, out)
         return out
 
@@ -994,22 +853,22 @@ class _Blend(torch.autograd.Function):
                 _take_premasked(epi, g)
             else:
                 act = out
-        lib = _lib.load()
-        g = g.contiguous()
-        g0, g1 = torch.empty_like(g), torch.empty_like(g)
-        gbeta = torch.empty_like(beta)
-        ws = _workspace("blend", lib.sngnn_blend_workspace_bytes(), g.device)
-        with torch.cuda.device(g.device):
-            if act is None:
-                rc = lib.sngnn_blend_backward(g.data_ptr(), out0.data_ptr(), out1.data_ptr(), beta.data_ptr(),
-                                              g.numel(), g0.data_ptr(), g1.data_ptr(), gbeta.data_ptr(),
-                                              ws.data_ptr(), _stream(g.device))
-            else:
-                rc = lib.sngnn_blend_backward_epilogue(g.data_ptr(), out0.data_ptr(), out1.data_ptr(), beta.data_ptr(),
-                                                       g.numel(), act.data_ptr(), float(epi.scale), g0.data_ptr(),
-                                                       g1.data_ptr(), gbeta.data_ptr(), ws.data_ptr(), _stream(g.device))
-        _lib.check(rc, "sngnn_blend_backward")
-        return g0, g1, gbeta, None
+        return (*_blend_backward(g, out0, out1, beta, act, epi), None)
+
+
+def _blend_backward(g, out0, out1, beta, act=None, epi=None):
+    """(g0, g1, d beta) of the blend; with ``act`` (the activated output ``epi`` left) relu' and the dropout mask
+    are applied to ``g`` in the same pass."""
+    g = g.contiguous()
+    g0, g1 = torch.empty_like(g), torch.empty_like(g)
+    gbeta = torch.empty_like(beta)
+    ws = _workspace("blend", _lib.load().sngnn_blend_workspace_bytes(), g.device)
+    if act is None:
+        _lib.call("sngnn_blend_backward", g.device, g, out0, out1, beta, g.numel(), g0, g1, gbeta, ws)
+    else:
+        _lib.call("sngnn_blend_backward_epilogue", g.device, g, out0, out1, beta, g.numel(), act, float(epi.scale),
+                  g0, g1, gbeta, ws)
+    return g0, g1, gbeta
 
 
 class _BlendHead(torch.autograd.Function):
@@ -1021,32 +880,17 @@ class _BlendHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, out0, out1, beta, head):
-        lib = _lib.load()
         n, c = out0.shape
         out = torch.empty_like(out0)
-        ws = _workspace("head", lib.sngnn_head_workspace_bytes(n), out0.device)
-        with torch.cuda.device(out0.device):
-            rc = lib.sngnn_head_nll_blend(out0.data_ptr(), out1.data_ptr(), beta.data_ptr(), head.y.data_ptr(),
-                                          head.sel.data_ptr(), n, c, head.sets, head.n_a, head.n_b,
-                                          out.data_ptr() if head.grad else None, None if head.grad else out.data_ptr(),
-                                          head.metrics.data_ptr(), ws.data_ptr(), _stream(out0.device))
-        _lib.check(rc, "sngnn_head_nll_blend")
+        ws = _workspace("head", _lib.load().sngnn_head_workspace_bytes(n), out0.device)
+        _lib.call("sngnn_head_nll_blend", out0.device, out0, out1, beta, head.y, head.sel, n, c, head.sets, head.n_a,
+                  head.n_b, out if head.grad else None, None if head.grad else out, head.metrics, ws)
         ctx.save_for_backward(out0, out1, beta)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        out0, out1, beta = ctx.saved_tensors
-        lib = _lib.load()
-        g = g.contiguous()
-        g0, g1 = torch.empty_like(g), torch.empty_like(g)
-        gbeta = torch.empty_like(beta)
-        ws = _workspace("blend", lib.sngnn_blend_workspace_bytes(), g.device)
-        with torch.cuda.device(g.device):
-            rc = lib.sngnn_blend_backward(g.data_ptr(), out0.data_ptr(), out1.data_ptr(), beta.data_ptr(), g.numel(),
-                                          g0.data_ptr(), g1.data_ptr(), gbeta.data_ptr(), ws.data_ptr(), _stream(g.device))
-        _lib.check(rc, "sngnn_blend_backward")
-        return g0, g1, gbeta, None
+        return (*_blend_backward(g, *ctx.saved_tensors), None)
 
 
 def blend_head(out0: torch.Tensor, out1: torch.Tensor, beta: torch.Tensor, head: "HeadEpilogue") -> Optional[torch.Tensor]:
@@ -1080,25 +924,26 @@ def blend(out0: torch.Tensor, out1: torch.Tensor, beta: torch.Tensor,
     return beta * out0 + (1 - beta) * out1
 
 
+def _head_nll(logits, y, row_mask_u8, n_masked, out, want_grad: bool):
+    """``sngnn_head_nll``: (fp32 [2] = (mean NLL, n_correct) - ``out`` if given -, d loss / d logits or None)."""
+    z = logits.contiguous()
+    n, c = z.shape
+    grad = torch.empty_like(z) if want_grad else None
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=z.device)
+    ws = _workspace("head", _lib.load().sngnn_head_workspace_bytes(n), z.device)
+    _lib.call("sngnn_head_nll", z.device, z, y, row_mask_u8, n, c, int(n_masked), grad, out, ws)
+    return out, grad
+
+
 class _HeadNLL(torch.autograd.Function):
     """mean NLL of log_softmax(logits) over the masked rows; also returns the number
     of correctly classified masked rows (no gradient)."""
 
     @staticmethod
     def forward(ctx, logits, y, row_mask_u8, n_masked, out=None):
-        lib = _lib.load()
-        z = logits.contiguous()
-        n, c = z.shape
         need_grad = ctx.needs_input_grad[0]
-        grad = torch.empty_like(z) if need_grad else None
-        if out is None:
-            out = torch.empty(2, dtype=torch.float32, device=z.device)
-        ws = _workspace("head", lib.sngnn_head_workspace_bytes(n), z.device)
-        with torch.cuda.device(z.device):
-            rc = lib.sngnn_head_nll(z.data_ptr(), y.data_ptr(), row_mask_u8.data_ptr(), n, c,
-                                    int(n_masked), _lib.ptr(grad), out.data_ptr(), ws.data_ptr(),
-                                    _stream(z.device))
-        _lib.check(rc, "sngnn_head_nll")
+        out, grad = _head_nll(logits, y, row_mask_u8, n_masked, out, need_grad)
         if need_grad:
             ctx.save_for_backward(grad)
         loss, correct = out[0], out[1]
@@ -1117,17 +962,7 @@ def head_nll_with_grad(logits: torch.Tensor, y: torch.Tensor, row_mask_u8: torch
     d loss / d logits).  A trainer calls ``logits.backward(grad)`` with it - the same
     gradient ``loss.backward()`` produces through :func:`head_nll`, without the ones-fill and
     the ``grad * 1`` pass over [N, C] that the generic autograd seam costs."""
-    lib = _lib.load()
-    z = logits.detach().contiguous()
-    n, c = z.shape
-    grad = torch.empty_like(z)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=z.device)
-    ws = _workspace("head", lib.sngnn_head_workspace_bytes(n), z.device)
-    with torch.cuda.device(z.device):
-        rc = lib.sngnn_head_nll(z.data_ptr(), y.data_ptr(), row_mask_u8.data_ptr(), n, c, int(n_masked),
-                                grad.data_ptr(), out.data_ptr(), ws.data_ptr(), _stream(z.device))
-    _lib.check(rc, "sngnn_head_nll")
+    out, grad = _head_nll(logits.detach(), y, row_mask_u8, n_masked, out, True)
     return (out[0], out[1]), grad
 
 
@@ -1146,14 +981,10 @@ def head_nll2(logits: torch.Tensor, y: torch.Tensor, row_sets_u8: torch.Tensor, 
         out = torch.empty(4, dtype=torch.float32, device=logits.device)
     elif out.dtype != torch.float32 or out.numel() != 4 or not out.is_contiguous() or out.device != logits.device:
         raise ValueError("out must be a contiguous float32 tensor of 4 elements on the logits' device")
-    lib = _lib.load()
     z = logits.detach().contiguous()
     n, c = z.shape
-    ws = _workspace("head", lib.sngnn_head_workspace_bytes(n), z.device)
-    with torch.cuda.device(z.device):
-        _lib.check(lib.sngnn_head_nll2(z.data_ptr(), y.contiguous().data_ptr(), row_sets_u8.contiguous().data_ptr(),
-                                       n, c, int(n_a), int(n_b), out.data_ptr(), ws.data_ptr(), _stream(z.device)),
-                   "sngnn_head_nll2")
+    ws = _workspace("head", _lib.load().sngnn_head_workspace_bytes(n), z.device)
+    _lib.call("sngnn_head_nll2", z.device, z, y.contiguous(), row_sets_u8.contiguous(), n, c, int(n_a), int(n_b), out, ws)
     return out
 
 

@@ -82,10 +82,6 @@ def union_graph(edge_index: torch.Tensor, num_nodes: int, replicas: int, add_loo
 # ---------------------------------------------------------------------------------------------
 # operators
 # ---------------------------------------------------------------------------------------------
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def replica_unpack(hs: torch.Tensor, bias: Optional[torch.Tensor], replicas: int, unit: Optional["ops.UnitRows"] = None):
     """``sngnn_replica_unpack``: [N, R C] -> the union table [R N, C] (+ bias [R, C]); fills ``unit`` (unit rows,
     norms and, when it wants them, the filter rows) from the same pass."""
@@ -102,10 +98,7 @@ def replica_unpack(hs: torch.Tensor, bias: Optional[torch.Tensor], replicas: int
         fb = ops.filter_row_bytes(c) if unit.want_filter else 0
         filt = unit.filt = torch.empty((replicas * n, fb), dtype=torch.uint8, device=hs.device) if fb else None
     b = None if bias is None else bias.detach().contiguous()
-    with torch.cuda.device(hs.device):
-        rc_ = _lib.load().sngnn_replica_unpack(hs.data_ptr(), _lib.ptr(b), n, replicas, c, h.data_ptr(), _lib.ptr(nn_),
-                                               _lib.ptr(nrm), _lib.ptr(filt), _stream(hs.device))
-    _lib.check(rc_, "sngnn_replica_unpack")
+    _lib.call("sngnn_replica_unpack", hs.device, hs, b, n, replicas, c, h, nn_, nrm, filt)
     return h
 
 
@@ -119,11 +112,8 @@ def replica_wgrad(g: torch.Tensor, x: torch.Tensor, replicas: int):
         raise ValueError("g must be [R N, C]")
     gw = torch.empty((replicas * c, f), dtype=torch.float32, device=g.device)
     gb = torch.empty(replicas * c, dtype=torch.float32, device=g.device)
-    ws = ops._workspace("replica_wgrad", lib.sngnn_replica_wgrad_workspace_bytes(n, replicas, c, f), g.device)
-    with torch.cuda.device(g.device):
-        rc = lib.sngnn_replica_wgrad(g.data_ptr(), x.data_ptr(), n, replicas, c, f, gw.data_ptr(), gb.data_ptr(),
-                                     ws.data_ptr(), _stream(g.device))
-    _lib.check(rc, "sngnn_replica_wgrad")
+    ws = _lib.workspace("replica_wgrad", lib.sngnn_replica_wgrad_workspace_bytes(n, replicas, c, f), g.device)
+    _lib.call("sngnn_replica_wgrad", g.device, g, x, n, replicas, c, f, gw, gb, ws)
     return gw, gb
 
 
@@ -144,13 +134,10 @@ def replica_head(logits: torch.Tensor, y: torch.Tensor, sel: torch.Tensor, count
         raise ValueError("replica_head: out must be an fp32 [R, 2 sets] view with unit column stride")
     z1 = None if logits1 is None else logits1.detach().contiguous()
     g = torch.empty_like(z) if grad else None
-    lib = _lib.load()
-    ws = ops._workspace("replica_head", lib.sngnn_replica_head_workspace_bytes(r), z.device)
-    with torch.cuda.device(z.device):
-        rc = lib.sngnn_replica_head_nll(z.data_ptr(), _lib.ptr(z1), _lib.ptr(beta), y.data_ptr(), sel.data_ptr(),
-                                        counts.data_ptr(), n, r, c, sets, _lib.ptr(g), out.data_ptr(), out.stride(0),
-                                        ws.data_ptr(), _stream(z.device))
-    _lib.check(rc, "sngnn_replica_head_nll")
+    ws = _lib.workspace("replica_head", _lib.load().sngnn_replica_head_workspace_bytes(r), z.device)
+    # (``out`` goes in as an address beside its row stride: the one argument whose rows may be strided)
+    _lib.call("sngnn_replica_head_nll", z.device, z, z1, beta, y, sel, counts, n, r, c, sets, g, out.data_ptr(),
+              out.stride(0), ws)
     return g
 
 
@@ -160,22 +147,15 @@ def replica_blend_backward(g, out0, out1, beta):
     r = beta.numel()
     g = g.contiguous()
     g0, g1, gbeta = torch.empty_like(g), torch.empty_like(g), torch.empty_like(beta)
-    ws = ops._workspace("replica_blend", lib.sngnn_replica_blend_workspace_bytes(r), g.device)
-    with torch.cuda.device(g.device):
-        rc = lib.sngnn_replica_blend_backward(g.data_ptr(), out0.data_ptr(), out1.data_ptr(), beta.data_ptr(),
-                                              g.numel() // r, r, g0.data_ptr(), g1.data_ptr(), gbeta.data_ptr(),
-                                              ws.data_ptr(), _stream(g.device))
-    _lib.check(rc, "sngnn_replica_blend_backward")
+    ws = _lib.workspace("replica_blend", lib.sngnn_replica_blend_workspace_bytes(r), g.device)
+    _lib.call("sngnn_replica_blend_backward", g.device, g, out0, out1, beta, g.numel() // r, r, g0, g1, gbeta, ws)
     return g0, g1, gbeta
 
 
 def replica_blend_forward(out0, out1, beta):
     r = beta.numel()
     out = torch.empty_like(out0)
-    with torch.cuda.device(out0.device):
-        rc = _lib.load().sngnn_replica_blend_forward(out0.data_ptr(), out1.data_ptr(), beta.data_ptr(),
-                                                     out0.numel() // r, r, out.data_ptr(), _stream(out0.device))
-    _lib.check(rc, "sngnn_replica_blend_forward")
+    _lib.call("sngnn_replica_blend_forward", out0.device, out0, out1, beta, out0.numel() // r, r, out)
     return out
 
 

@@ -23,19 +23,13 @@ def _x(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.float32).contiguous()
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def cosine_similarity_dense_small(x: torch.Tensor) -> torch.Tensor:
     """dense.py:138-141: S = normalize(x) @ normalize(x).T, [N, N] (matrix cores: exact bf16 split of
     both operands, fp32 accumulation - an fp32 contraction's rounding; csrc/toolbox.hip)."""
     x = _x(x)
     n, f = x.shape
     s = torch.empty((n, n), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().sngnn_cosine_dense(x.data_ptr(), n, f, s.data_ptr(), _stream(x))
-    _lib.check(rc, "sngnn_cosine_dense")
+    _lib.call("sngnn_cosine_dense", x.device, x, n, f, s)
     return s
 
 
@@ -47,10 +41,7 @@ def edge_cosine(x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         raise ValueError("x and edge_index must be on the same device")
     e = ei.size(1)
     sim = torch.empty(e, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().sngnn_edge_cosine(x.data_ptr(), x.size(0), x.size(1), ei.data_ptr(), e,
-                                           sim.data_ptr(), _stream(x))
-    _lib.check(rc, "sngnn_edge_cosine")
+    _lib.call("sngnn_edge_cosine", x.device, x, x.size(0), x.size(1), ei, e, sim)
     return sim
 
 
@@ -70,11 +61,7 @@ def class_block_sums(x: torch.Tensor, y: torch.Tensor, n_classes: int):
     y32 = y.to(device=x.device, dtype=torch.int32).contiguous()
     sums = torch.zeros((n_classes, n_classes), dtype=torch.float64, device=x.device)
     diag = torch.zeros(1, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().sngnn_cosine_class_sums(x.data_ptr(), x.size(0), x.size(1),
-                                                 y32.data_ptr(), n_classes, sums.data_ptr(),
-                                                 diag.data_ptr(), _stream(x))
-    _lib.check(rc, "sngnn_cosine_class_sums")
+    _lib.call("sngnn_cosine_class_sums", x.device, x, x.size(0), x.size(1), y32, n_classes, sums, diag)
     return sums, diag
 
 
@@ -132,10 +119,7 @@ def _hist_scan(x, y32, edges, bins):
     stats = torch.empty(3, dtype=torch.float64, device=x.device)
     ws = torch.empty(max(int(lib.sngnn_cosine_hist_workspace_bytes(n, f, bins, groups)), 256), dtype=torch.uint8,
                      device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.sngnn_cosine_hist(x.data_ptr(), n, f, _lib.ptr(y32), edges.data_ptr(), bins, counts.data_ptr(),
-                                   stats.data_ptr(), ws.data_ptr(), _stream(x))
-    _lib.check(rc, "sngnn_cosine_hist")
+    _lib.call("sngnn_cosine_hist", x.device, x, n, f, y32, edges, bins, counts, stats, ws)
     return counts, stats
 
 
@@ -227,10 +211,7 @@ def segment_mean(val: torch.Tensor, index: torch.Tensor, length: int):
         raise ValueError("val and index must be 1-D and of one length")
     mean = torch.empty(int(length), dtype=torch.float32, device=val.device)
     cnt = torch.empty(int(length), dtype=torch.int32, device=val.device)
-    with torch.cuda.device(val.device):
-        rc = _lib.load().sngnn_segment_mean(val.data_ptr(), idx.data_ptr(), val.numel(), int(length),
-                                            mean.data_ptr(), cnt.data_ptr(), _stream(val))
-    _lib.check(rc, "sngnn_segment_mean")
+    _lib.call("sngnn_segment_mean", val.device, val, idx, val.numel(), int(length), mean, cnt)
     return mean, cnt
 
 
@@ -326,12 +307,8 @@ class _SparseCols:
         a = a.to(self.device, torch.int64).contiguous()
         b = b.to(self.device, torch.int64).contiguous()
         out = torch.empty(a.numel(), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = _lib.load().sngnn_sparse_pair_dot(self.colptr.data_ptr(), self.rowidx.data_ptr(),
-                                                   self.vals.data_ptr(), self.shape[1], a.data_ptr(),
-                                                   b.data_ptr(), a.numel(), out.data_ptr(),
-                                                   torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "sngnn_sparse_pair_dot")
+        _lib.call("sngnn_sparse_pair_dot", self.device, self.colptr, self.rowidx, self.vals, self.shape[1], a, b,
+                  a.numel(), out)
         return out
 
     def dense(self) -> torch.Tensor:
@@ -421,10 +398,7 @@ def knn_graph(x: torch.Tensor, k: int, exclude_self: bool = True):
     idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
     sim = torch.empty((n, k), dtype=torch.float32, device=x.device)
     ws = torch.empty(max(int(lib.sngnn_knn_workspace_bytes(n, int(k))), 256), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = lib.sngnn_knn_graph(x.data_ptr(), n, f, int(k), int(bool(exclude_self)), idx.data_ptr(),
-                                 sim.data_ptr(), ws.data_ptr(), _stream(x))
-    _lib.check(rc, "sngnn_knn_graph")
+    _lib.call("sngnn_knn_graph", x.device, x, n, f, int(k), int(bool(exclude_self)), idx, sim, ws)
     return idx.long(), sim
 
 
