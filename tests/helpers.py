@@ -37,6 +37,108 @@ def random_graph(n, e, seed, hubs=()):
     return torch.from_numpy(np.stack([key // n, key % n]))
 
 
+REGIMES = ("normal", "parallel", "sparse", "tiny", "near_eps")
+
+
+def regime_rows(n, c, seed, kind):
+    """Feature rows of the regimes a kernel meets: ``normal`` randn; ``parallel`` nearly parallel rows (every
+    cosine within 1e-3 of 1: a deep layer's input); ``tiny`` a 1e-30 .. 1 channel range; ``near_eps`` unit rows
+    scaled by 10 ** U(-15, -9) - norms on both sides of F.normalize's 1e-12 clamp while every square stays a
+    normal fp32 number - with every third row plain randn; ``sparse`` post-ReLU rows with exact zeros and whole
+    zero rows.  Always h[5] == h[6] (an exact tie) and h[9] == 0."""
+    assert kind in REGIMES, kind
+    g = torch.Generator().manual_seed(seed)
+    if kind == "normal":
+        h = torch.randn(n, c, generator=g)
+    elif kind == "parallel":           # nearly parallel rows: every cosine within 1e-3 of 1
+        h = torch.randn(1, c, generator=g) + 1e-2 * torch.randn(n, c, generator=g)
+    elif kind == "tiny":               # components far below fp16's range before the scaling
+        h = torch.randn(n, c, generator=g) * torch.logspace(-30, 0, c).view(1, -1)
+    elif kind == "near_eps":
+        h = torch.nn.functional.normalize(torch.randn(n, c, generator=g), dim=1)
+        h = h * 10.0 ** (torch.rand(n, 1, generator=g) * 6 - 15)
+        h[::3] = torch.randn(n, c, generator=g)[::3]
+    else:                              # sparse non-negative (bag-of-words after a ReLU)
+        h = torch.relu(torch.randn(n, c, generator=g) - 1.0)
+    h[5] = h[6]
+    h[9] = 0.0
+    return h
+
+
+def regime_inputs(n, c, kind):
+    """(h, gout) of one backward-regime case: regime_rows + a power-of-two multiple of the tied row."""
+    h = regime_rows(n, c, 7 + c, kind)
+    h[7] = 2 * h[6]
+    gout = torch.randn(n, c, generator=torch.Generator().manual_seed(1000 + c))
+    return h, gout
+
+
+REGIME_HUB_SOURCE = 4
+REGIME_ISOLATED = 50
+
+
+def regime_edges(n=3000):
+    """One edge list with every row class of the kernels: split targets (in-degree > 128: node 0 with an
+    in-edge from EVERY other node, 900, 500, 300, 140, 129), wave targets (17 .. 128: 128, 60, 20, 17 and a
+    block of 40 rows of random degree in that range), small targets (the rest, 16 among them), a hub SOURCE
+    (node 4: n / 2 out-edges) and 50 nodes without any in-edge (the last 50) - the zero row 9 and the tied
+    rows 5, 6, 7 are targets and sources like any other; targets 1000 .. 1004 and the block 800 .. 839 lie in
+    the node range (n // 4, n // 4 + n // 3).  Sparse enough that most nodes are small on both sides."""
+    hubs = ((3, 900), (9, 300), (11, 140), (12, 60), (13, 20), (1000, 500), (1001, 129), (1002, 128),
+            (1003, 17), (1004, 16))
+    ei = random_graph(n, 3 * n, seed=3, hubs=hubs)
+    rng = np.random.default_rng(5)
+    block = [(int(s), t) for t in range(800, 840)
+             for s in rng.choice(n, size=int(rng.integers(17, 129)), replace=False)]
+    every = torch.arange(1, n)
+    ei = torch.cat([ei, torch.tensor(block).t(), torch.stack([every, torch.zeros_like(every)]),
+                    torch.stack([torch.full((n // 2,), REGIME_HUB_SOURCE), torch.arange(n // 2) * 2 + 1])], 1)
+    ei = torch.unique(ei, dim=1)
+    return ei[:, ei[1] < n - REGIME_ISOLATED]
+
+
+def csr_of_edge_list(ei, n):
+    """CSR by target of an edge list (edge order kept inside a row): rowptr [n + 1], col [E], and the
+    permutation ``order`` with col == ei[0][order]."""
+    order = torch.argsort(ei[1], stable=True)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64)
+    rowptr[1:] = torch.cumsum(torch.bincount(ei[1], minlength=n), 0)
+    return rowptr, ei[0][order], order
+
+
+def oracle_fixed_mask(h, rowptr, col, kept, gout, row_offset=0):
+    """The oracle's own blocks (F.normalize, O.edge_cosine, O.scatter_mean) on a CSR with the kept mask FIXED,
+    in h's dtype, and autograd's gradient of <out, gout>: (out [N, C], grad_h [N_total, C]).  For a node-range
+    partition the rows are the owned targets and ``col`` / ``h`` are global."""
+    rowptr, col = torch.as_tensor(np.asarray(rowptr)).long(), torch.as_tensor(np.asarray(col)).long()
+    n = rowptr.numel() - 1
+    dst = torch.repeat_interleave(torch.arange(n), rowptr.diff())
+    kept = torch.ones(col.numel(), dtype=torch.bool) if kept is None else torch.as_tensor(np.asarray(kept)).bool()
+    h = h.detach().clone().requires_grad_(True)
+    s = O.edge_cosine(torch.nn.functional.normalize(h, p=2., dim=-1), torch.stack([col, dst + row_offset]))
+    w = torch.where(kept, s, torch.zeros_like(s))
+    out = O.scatter_mean(w.view(-1, 1) * h.index_select(0, col), dst, n)
+    (out * gout.to(h.dtype)).sum().backward()
+    return out.detach(), h.grad
+
+
+def row_classes(rowptr, h, row_offset=0, loops_kept=False):
+    """Names -> bool masks over the N_total feature rows, for reporting a gradient's worst element per class:
+    zero rows, eps-clamped non-zero rows, the hub source, and the owned targets by the kernels' row class
+    (in-degree > 128 split, 17 .. 128 wave, else small; isolated: no in-edge but - where loops are kept - its own)."""
+    h = torch.as_tensor(h).double()
+    nrm = h.norm(dim=1)
+    deg = torch.as_tensor(np.asarray(rowptr)).long().diff()
+    lo = int(row_offset)
+    own = lambda m: torch.zeros(h.size(0), dtype=torch.bool).index_put_((torch.arange(lo, lo + deg.numel()),), m)
+    iso = deg <= (1 if loops_kept else 0)
+    hub = torch.zeros(h.size(0), dtype=torch.bool)
+    hub[REGIME_HUB_SOURCE] = True
+    return {"zero": nrm == 0, "clamped": (nrm > 0) & (nrm < 1e-12), "hub-src": hub,
+            "split": own(deg > 128), "wave": own((deg > 16) & (deg <= 128)), "small": own((deg <= 16) & ~iso),
+            "isolated": own(iso)}
+
+
 def log_operator_rows(differ, rows, label=None):
     """One operator-level comparison for the pytest summary (tests/conftest.py)."""
     import os

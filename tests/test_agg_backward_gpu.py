@@ -4,7 +4,8 @@ import pytest
 import torch
 
 from oracle import sngnn_oracle as O
-from tests.helpers import assert_close, random_graph
+from tests import arbiter
+from tests.helpers import assert_close, oracle_fixed_mask, random_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +80,40 @@ def test_eps_clamped_rows(cuda):
     h_gpu = h.to(cuda).requires_grad_(True)
     (ops.aggregate(h_gpu, g, None, 0.0) * gout.to(cuda)).sum().backward()
     assert_grad_close(h_gpu.grad, h_ref.grad, "grad_h (eps rows)", rel=1e-4)
+    # The global scale above is set by rows 3 and 4 alone (their gradients are ~1e12 times an ordinary row's:
+    # n = h / 1e-12), so it says nothing about the rows that have them as neighbours.  Element by element
+    # against the float64 arbiter - on this graph, and on one where the two rows are also sources of a wave
+    # row (60 in-edges) and of a split row (300), without a selection and with top_k = 4, thr = 0.0 (where a
+    # zero-row source is kept: its cosine 0 passes >= thr).
+    n2 = 400
+    big = random_graph(n2, 2000, seed=6, hubs=((10, 60), (11, 300)))
+    big = torch.unique(torch.cat([big, torch.tensor([[3, 4, 3, 4], [10, 10, 11, 11]])], 1), dim=1)
+    h2 = torch.randn(n2, C, generator=torch.Generator().manual_seed(4))
+    h2[3] = 0.0
+    h2[4] = 1e-14
+    gout2 = torch.randn(n2, C, generator=torch.Generator().manual_seed(5))
+    for ei_c, nc, hc, gc in ((ei, n, h, gout), (big, n2, h2, gout2)):
+        for rem in (False, True):
+            gr = Graph(ei_c.to(cuda), nc, True, rem)
+            rowptr, col = gr.array("rowptr"), gr.array("col")
+            if nc == n2:
+                deg = np.diff(rowptr)
+                assert 16 < deg[10] <= 128 < deg[11]
+                assert all(s in col[rowptr[t]:rowptr[t + 1]] for s in (3, 4) for t in (10, 11))
+            for k, thr in ((None, 0.0), (4, 0.0)):
+                _, wsel, *_ = ops.aggregate_forward(gr, hc.to(cuda), k, thr, save_for_backward=True)
+                kept = (wsel > -3.0).cpu()
+                arb = arbiter.aggregate(rowptr, col, kept, hc, gc)
+                out32, grad32 = oracle_fixed_mask(hc, rowptr, col, kept, gc)
+                what = f"eps rows n={nc} rem={rem} k={k}"
+                k_out, _ = arbiter.reference_units(out32, arb["out"], arb["MAG_out"], what + " oracle out")
+                k_grad, _ = arbiter.reference_units(grad32, arb["grad"], arb["MAG_grad"], what + " oracle grad_h")
+                hg = hc.to(cuda).requires_grad_(True)
+                o = ops.aggregate(hg, gr, k, thr)
+                o.backward(gc.to(cuda))
+                assert_grad_close(hg.grad, grad32, what + " grad_h", rel=1e-4)
+                arbiter.check(o.detach().cpu(), arb["out"], arb["MAG_out"], k_out, what + " out")
+                arbiter.check(hg.grad.cpu(), arb["grad"], arb["MAG_grad"], k_grad, what + " grad_h")
 
 
 @pytest.mark.parametrize("n,e,C,hubs,src_min", [(120, 900, 5, ((1, 100),), 0),
@@ -234,11 +269,14 @@ def test_node_centric_backward_equals_the_two_passes(cuda, n, e, C, hubs, rem, k
     gout = torch.randn(n, C, generator=gen).to(cuda)
 
     def close(x, y):
-        return float((x - y).abs().max()) <= 2e-6 * max(float(y.abs().max()), 1e-30)
+        # element by element against the size of what each element sums (tests/arbiter.py) - a global maximum
+        # is set by the zero row 7 (n = h / 1e-12) and would compare that row alone
+        return bool(((x - y).abs().cpu().double() <= 2e-6 * mag).all())
 
     try:
         g = Graph(ei, n, True, rem)
         _, wsel, *_ = ops.aggregate_forward(g, h, k, thr, save_for_backward=True)
+        mag = arbiter.aggregate(g.array("rowptr"), g.array("col"), (wsel > -3.0).cpu(), h.cpu(), gout.cpu())["MAG_grad"]
         two = _backward_in_mode(lib, 1, g, h, gout, wsel, None)
         assert torch.equal(_backward_in_mode(lib, 2, g, h, gout, wsel, None), two)
         if k is not None:

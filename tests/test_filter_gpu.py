@@ -8,24 +8,10 @@ import pytest
 import torch
 
 from tests.helpers import random_graph
+from tests.helpers import regime_rows as _rows
 
 pytestmark = pytest.mark.gpu
 FILT_EPS = 1.1e-3          # csrc/agg_fwd_filter.h
-
-
-def _rows(n, c, seed, kind):
-    g = torch.Generator().manual_seed(seed)
-    if kind == "normal":
-        h = torch.randn(n, c, generator=g)
-    elif kind == "parallel":           # nearly parallel rows: every cosine within 1e-3 of 1
-        h = torch.randn(1, c, generator=g) + 1e-2 * torch.randn(n, c, generator=g)
-    elif kind == "tiny":               # components far below fp16's range before the scaling
-        h = torch.randn(n, c, generator=g) * torch.logspace(-30, 0, c).view(1, -1)
-    else:                              # sparse non-negative (bag-of-words after a ReLU)
-        h = torch.relu(torch.randn(n, c, generator=g) - 1.0)
-    h[5] = h[6]
-    h[9] = 0.0
-    return h
 
 
 @pytest.mark.parametrize("c", [36, 40, 48, 64, 100, 128, 256, 512])

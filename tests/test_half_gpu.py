@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from sngnn_amd import _lib, ops, synth
 from sngnn_amd.graph import Graph
-from tests.helpers import check_selection, oracle_aggregate, random_graph
+from tests.helpers import REGIMES, check_selection, oracle_aggregate, random_graph, regime_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +117,25 @@ def test_contract_grid(cuda, graphs, D, C):
                                bwd_modes=(0, 1, 2) if (k == 16 and thr == 0.0) else (0,))
                 cases += 1
     print(f"{D} C={C}: {cases} cases bit for bit")
+
+
+@pytest.mark.parametrize("D", DTYPES, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("C", [7, 40])
+@pytest.mark.parametrize("kind", REGIMES)
+def test_contract_on_the_regimes(cuda, graphs, D, C, kind):
+    """The contract is bit for bit against the fp32 path, so it inherits that path's checks against the float64
+    arbiter (tests/test_backward_regimes_gpu.py) only on the rows those checks ran on: the same five regimes,
+    rounded to D.  In fp16 the ``tiny`` and ``near_eps`` rows become subnormals and zeros, and a row of out or
+    grad_h may overflow: "the fp32 result rounded once" holds there as well (+-inf equals +-inf), so nothing
+    is filtered out."""
+    gs, _, n = graphs
+    h = regime_inputs(n, C, kind)[0].to(cuda).to(D)
+    for rem, g in gs.items():
+        for k, thr in ((16, 0.0), (3, 0.3), (None, 0.0)):
+            check_contract(g, h, k, thr, f"{D} {kind} C={C} rem={rem} k={k} thr={thr}", bwd_modes=(0, 1, 2))
+    hf = h.float()
+    print(f"{D} {kind} C={C}: {int((hf.abs().sum(1) == 0).sum())} zero rows, "
+          f"{int(((hf != 0) & (hf.abs() < torch.finfo(D).tiny)).sum())} subnormal elements after rounding")
 
 
 @pytest.mark.parametrize("D", DTYPES, ids=["bf16", "fp16"])
