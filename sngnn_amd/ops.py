@@ -493,6 +493,36 @@ def attention(h: torch.Tensor, graph: Graph) -> torch.Tensor:
     return _Attention.apply(h, graph)
 
 
+def signed_forward(graph: Graph, wh: torch.Tensor, coef: torch.Tensor, c2: torch.Tensor):
+    """``sngnn_signed_forward``: (out [N, C], s [E'] the cosines in the graph's CSR order).  ``coef`` [E'] = a_e
+    in CSR order, ``c2`` [2] device scalars (c_pos, c_neg)."""
+    wh = _check_rows(wh, graph.num_total_nodes, "wh")
+    c = wh.size(1)
+    if coef.dtype != torch.float32 or coef.numel() != graph.num_edges or not coef.is_cuda:
+        raise ValueError("coef must be a float32 GPU tensor with one entry per edge of the graph")
+    if c2.dtype != torch.float32 or c2.numel() != 2 or not c2.is_cuda:
+        raise ValueError("c2 must be a float32 GPU tensor of 2 elements")
+    coef, c2 = coef.contiguous(), c2.contiguous()
+    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=wh.device)
+    s = torch.empty(graph.num_edges, dtype=torch.float32, device=wh.device)
+    _lib.call("sngnn_signed_forward", wh.device, graph.handle, wh, c, coef, c2, out, s, graph.workspace(c))
+    return out, s
+
+
+def signed_backward(graph: Graph, wh: torch.Tensor, grad_out: torch.Tensor, coef: torch.Tensor, s: torch.Tensor,
+                    c2: torch.Tensor):
+    """``sngnn_signed_backward``: (grad_wh [N_total, C], u [E'] = s_e <G_i, Wh_j> in CSR order) from the forward's
+    saved cosines ``s``."""
+    wh = _check_rows(wh, graph.num_total_nodes, "wh")
+    g = _check_rows(grad_out.contiguous(), graph.num_nodes, "grad_out")
+    c = wh.size(1)
+    coef, c2, s = coef.contiguous(), c2.contiguous(), s.contiguous()
+    grad_wh = torch.empty_like(wh)
+    u = torch.empty_like(s)
+    _lib.call("sngnn_signed_backward", wh.device, graph.handle, wh, c, g, coef, s, c2, grad_wh, u, graph.workspace(c))
+    return grad_wh, u
+
+
 class _SignedPropagate(torch.autograd.Function):
     """GGCNlayer_SP's two signed propagations as ONE gather (models.py:1512-1519 + 1529-1537):
     ``c2[0] * prop_pos + c2[1] * prop_neg`` with prop_+- = (adj_remove_diag * sc * e_+-) @ Wh.
@@ -503,15 +533,8 @@ class _SignedPropagate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wh, coef, c2, graph):
         wh = _check_rows(wh, graph.num_total_nodes, "wh")
-        c = wh.size(1)
-        if coef.dtype != torch.float32 or coef.numel() != graph.num_edges or not coef.is_cuda:
-            raise ValueError("coef must be a float32 GPU tensor with one entry per edge of the graph")
-        if c2.dtype != torch.float32 or c2.numel() != 2 or not c2.is_cuda:
-            raise ValueError("c2 must be a float32 GPU tensor of 2 elements")
         coef, c2 = coef.contiguous(), c2.contiguous()
-        out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=wh.device)
-        s = torch.empty(graph.num_edges, dtype=torch.float32, device=wh.device)
-        _lib.call("sngnn_signed_forward", wh.device, graph.handle, wh, c, coef, c2, out, s, graph.workspace(c))
+        out, s = signed_forward(graph, wh, coef, c2)
         ctx.graph = graph
         ctx.save_for_backward(wh, coef, c2, s)
         return out
@@ -519,13 +542,7 @@ class _SignedPropagate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         wh, coef, c2, s = ctx.saved_tensors
-        graph = ctx.graph
-        g = _check_rows(g.contiguous(), graph.num_nodes, "grad_out")
-        c = wh.size(1)
-        grad_wh = torch.empty_like(wh)
-        u = torch.empty_like(s)
-        _lib.call("sngnn_signed_backward", wh.device, graph.handle, wh, c, g, coef, s, c2, grad_wh, u,
-                  graph.workspace(c))
+        grad_wh, u = signed_backward(ctx.graph, wh, g, coef, s, c2)
         pos, neg = s > 0, s < 0
         zero = torch.zeros((), dtype=torch.float32, device=s.device)
         kappa = torch.where(pos, c2[0], torch.where(neg, c2[1], zero))

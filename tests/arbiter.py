@@ -1,4 +1,5 @@
-"""Float64 arbiters of the aggregation and of the cosine attention: value AND term magnitude.
+"""Float64 arbiters of the aggregation, the cosine attention, the signed attention and the weighted propagation:
+value AND term magnitude.
 
 Plain float64 tensor arithmetic, no autograd, straight on a graph's own CSR (``g.array("rowptr")``,
 ``g.array("col")``; for a node-range partition the rows are the owned targets, ``col`` holds global ids and
@@ -28,6 +29,23 @@ Attention (oracle/sngnn_oracle.py: propagate_attention, segment_softmax): alpha_
 The softmax is not a sum, so "absolute values" needs a reading there: alpha_e > 0 is its own magnitude (an
 error of u in s_e moves alpha_e by ~u alpha_e: a relative error, which the gate's units already are), and
 DS_e = alpha_e (B_e + sum alpha B).
+
+Signed attention (csrc/signed_impl.h, ops._SignedPropagate; GGCNlayer_SP's use_sign branch after ``fcn``) with the
+SIGN of every edge fixed from outside - ``sign`` in {-1, 0, 1} per CSR edge, the kernel's own saved cosines supply
+it - which makes the operation smooth, as the kept mask does for the aggregation: kappa_e = c_pos (sign > 0) |
+c_neg (sign < 0) | 0, K_e = |kappa_e|, n_r = h_r / max(||h_r||, eps); per edge e = (j -> i), G = gout:
+  cosine         s_e = <n_i, n_j>                  S_e = <|n_i|, |n_j|>
+                 (evaluated as <h_i, h_j> / (max(||h_i||, eps) max(||h_j||, eps)): exactly 0 for orthogonal rows
+                 whose products are exact, so that ``sign(s_e)`` is a usable sign)
+  weight         w_e = a_e kappa_e s_e             W_e = |a_e| K_e S_e
+  forward        out_i = sum_e w_e h_j             OUT_i = sum_e W_e |h_j|
+  t_e = <G_i, h_j>, T_e = <|G_i|, |h_j|>;  u_e = s_e t_e, U_e = S_e T_e
+  d a_e = kappa_e u_e (K_e U_e);  d c_pos = sum_{sign > 0} a_e u_e (sum |a_e| U_e), d c_neg the same over sign < 0
+  message route  dh_j += w_e G_i                   (W_e |G_i|)
+  cosine route and normalisation as above with ds_e = a_e kappa_e t_e (DS_e = |a_e| K_e T_e) in a_e's place.
+
+Weighted propagation (ops.weighted_propagate, the use_sign=False branch: a sparse mm with one weight per entry):
+  out_i = sum_q w_q x_col(q),  grad_x_j = sum_q w_q G_i,  grad_w_q = <G_i, x_j>, each with |.| of every operand.
 """
 from __future__ import annotations
 
@@ -59,10 +77,10 @@ def _edges(rowptr, col, kept, row_offset):
     return dl, dl + int(row_offset), col, indeg.clamp_min(1).to(torch.float64)
 
 
-def _unit_rows(h):
+def _unit_rows(h, eps=EPS):
     nrm = h.norm(dim=1)
-    clamped = nrm < EPS
-    inv = 1.0 / nrm.clamp_min(EPS)
+    clamped = nrm < eps
+    inv = 1.0 / nrm.clamp_min(eps)
     return h * inv[:, None], inv, clamped
 
 
@@ -138,6 +156,63 @@ def attention(rowptr, col, h, gout=None, row_offset=0):
     return res
 
 
+def signed(rowptr, col, h, coef, c2, sign, gout=None, row_offset=0, eps=EPS, routes=True):
+    """The signed attention with every edge's sign fixed: dict(out, s [E] in CSR order; with ``gout`` grad [N_total, C],
+    u [E], grad_coef [E], grad_c2 [2]), each with its MAG_ (MAG_s is S).  ``coef`` [E] a_e, ``c2`` (c_pos, c_neg),
+    ``sign`` int [E] in {-1, 0, 1}.  ``routes=False`` stops after the per-edge and the scalar gradients (no grad)."""
+    h, coef, c2 = _t64(h), _t64(coef), _t64(c2)
+    dl, dg, src, deg = _edges(rowptr, col, None, row_offset)
+    n, c = deg.numel(), h.size(1)
+    sign = _cpu(sign).to(torch.int64)
+    assert sign.numel() == src.numel() == coef.numel() and bool((sign.abs() <= 1).all())
+    pos, neg = sign > 0, sign < 0
+    kappa = torch.where(pos, c2[0], torch.where(neg, c2[1], torch.zeros((), dtype=torch.float64)))
+    K, A = kappa.abs(), coef.abs()
+    un, inv, clamped = _unit_rows(h, eps)
+    # (raw dot, then the two inverse norms: orthogonal rows of exactly representable entries give s == 0 exactly,
+    # where a dot product of ROUNDED unit rows leaves float64 noise with a sign)
+    s, S = _dot(h[dg], h[src]) * (inv[dg] * inv[src]), _dot(un[dg].abs(), un[src].abs())
+    w, W = coef * kappa * s, A * K * S
+    out = torch.zeros(n, c, dtype=torch.float64).index_add_(0, dl, w[:, None] * h[src])
+    OUT = torch.zeros(n, c, dtype=torch.float64).index_add_(0, dl, W[:, None] * h[src].abs())
+    res = dict(out=out, MAG_out=OUT, s=s, MAG_s=S)
+    if gout is None:
+        return res
+    g = _t64(gout)
+    t, T = _dot(g[dl], h[src]), _dot(g[dl].abs(), h[src].abs())
+    u, U = s * t, S * T
+    au, AU = coef * u, A * U
+    zero = torch.zeros_like(au)
+    res.update(u=u, MAG_u=U, grad_coef=kappa * u, MAG_grad_coef=K * U,
+               grad_c2=torch.stack([torch.where(pos, au, zero).sum(), torch.where(neg, au, zero).sum()]),
+               MAG_grad_c2=torch.stack([torch.where(pos, AU, zero).sum(), torch.where(neg, AU, zero).sum()]))
+    if not routes:
+        return res
+    ds, DS = coef * kappa * t, A * K * T
+    dh = torch.zeros_like(h).index_add_(0, src, w[:, None] * g[dl])
+    DH = torch.zeros_like(h).index_add_(0, src, W[:, None] * g[dl].abs())
+    dn, DN = _cosine_route(ds, DS, un, dg, src, h.size(0))
+    res["grad"], res["MAG_grad"] = _normalize_backward(dh, DH, dn, DN, un, inv, clamped)
+    return res
+
+
+def weighted(rowptr, col, w, x, gout=None, row_offset=0):
+    """The weighted gather-sum: dict(out [N, C]; with ``gout`` grad_x [N_total, C], grad_w [E]), each with its MAG_."""
+    x, w = _t64(x), _t64(w)
+    dl, _, src, deg = _edges(rowptr, col, None, row_offset)
+    n, c = deg.numel(), x.size(1)
+    assert w.numel() == src.numel()
+    res = dict(out=torch.zeros(n, c, dtype=torch.float64).index_add_(0, dl, w[:, None] * x[src]),
+               MAG_out=torch.zeros(n, c, dtype=torch.float64).index_add_(0, dl, w.abs()[:, None] * x[src].abs()))
+    if gout is None:
+        return res
+    g = _t64(gout)
+    res.update(grad_x=torch.zeros_like(x).index_add_(0, src, w[:, None] * g[dl]),
+               MAG_grad_x=torch.zeros_like(x).index_add_(0, src, w.abs()[:, None] * g[dl].abs()),
+               grad_w=_dot(g[dl], x[src]), MAG_grad_w=_dot(g[dl].abs(), x[src].abs()))
+    return res
+
+
 # ------------------------------------------------------------------ the gate
 
 def units(got, val, mag):
@@ -171,6 +246,7 @@ def gate_units(k_ref):
 def check(got, val, mag, k_ref, what):
     """|got - val| <= 4 max(K_ref, 2) 2^-24 MAG element by element, exactly 0 where MAG == 0; no exemptions.
     Returns (worst element in units, the per-row worst [rows])."""
+    got, val, mag = (_t64(v).reshape(-1, 1) if _t64(v).dim() == 1 else _t64(v) for v in (got, val, mag))   # per-edge vectors
     u, zero = units(got, val, mag)
     g = _t64(got)
     nz = int((g[zero] != 0).sum())

@@ -73,6 +73,109 @@ def regime_inputs(n, c, kind):
     return h, gout
 
 
+SIGNED_REGIMES = REGIMES + ("antiparallel", "lattice")
+SIGNED_C2 = ((0.5, -0.3), (0.0, 0.7), (-1.25, -1.25))      # (c_pos, c_neg): mixed signs, a dead branch, equal and negative
+LATTICE_MIN_SHARE = 0.03
+
+
+def signed_coef(e, seed):
+    """a_e of the signed-attention tests: signed, randn x 10 ** U(-3, 1), every 17th entry exactly 0 (the kernel takes
+    any float; the model's own coef is positive)."""
+    g = torch.Generator().manual_seed(seed)
+    a = torch.randn(e, generator=g) * 10.0 ** (torch.rand(e, generator=g) * 4 - 3)
+    a[::17] = 0.0
+    return a
+
+
+def signed_inputs(n, c, kind):
+    """(h, gout, coef_of, c2 cases) of one signed-attention case; ``coef_of(E)`` gives a_e for a graph of E edges.
+    The five REGIMES: regime_inputs unchanged.  ``antiparallel``: the ``parallel`` rows times a random +-1 per row -
+    every cosine within 1e-3 of +1 or of -1, about half the edges on each side - with h[7] = -2 h[6], an exact
+    anti-tie.  ``lattice``: rows of integers in {-1, 0, 1} (``LATTICE_VALUES``) times a power of two in
+    2^-20 .. 2^20 per row: every partial sum of a raw dot product is exact in fp32 in any order, and many pairs
+    have a cosine of exactly 0 on overlapping supports (S_e > 0): kappa's third branch."""
+    assert kind in SIGNED_REGIMES, kind
+    if kind in REGIMES:
+        h, gout = regime_inputs(n, c, kind)
+    else:
+        g = torch.Generator().manual_seed(7 + c)
+        if kind == "antiparallel":
+            h = regime_rows(n, c, 7 + c, "parallel")
+            h = h * (torch.randint(0, 2, (n, 1), generator=g) * 2 - 1).float()
+            h[5] = h[6]
+            h[7] = -2 * h[6]
+        else:
+            lo, hi = LATTICE_VALUES
+            h = torch.randint(lo, hi + 1, (n, c), generator=g).float() * 2.0 ** torch.randint(-20, 21, (n, 1), generator=g).float()
+            h[5] = h[6]
+            h[7] = 2 * h[6]
+        h[9] = 0.0
+        gout = torch.randn(n, c, generator=torch.Generator().manual_seed(1000 + c))
+    return h, gout, (lambda e: signed_coef(e, 2000 + c)), SIGNED_C2
+
+
+LATTICE_VALUES = (-1, 1)
+
+
+def lattice_zero_share(h, rowptr, col, row_offset=0):
+    """Share of the CSR edges whose float64 cosine is exactly 0 although the two rows' supports overlap."""
+    rowptr, col = torch.as_tensor(np.asarray(rowptr)).long(), torch.as_tensor(np.asarray(col)).long()
+    dst = torch.repeat_interleave(torch.arange(rowptr.numel() - 1), rowptr.diff()) + row_offset
+    h64 = h.double()
+    d, dabs = (h64[dst] * h64[col]).sum(1), (h64[dst].abs() * h64[col].abs()).sum(1)
+    return float(((d == 0) & (dabs > 0)).double().mean())
+
+
+def assert_lattice_share(h, rowptr, col, row_offset=0):
+    share = lattice_zero_share(h, rowptr, col, row_offset)
+    assert share >= LATTICE_MIN_SHARE, f"lattice C={h.size(1)}: only {share:.2%} of the edges have s == 0 with S > 0"
+    return share
+
+
+def adj_with_diagonal(ei, n):
+    """Edge list (source, target) of ``ei`` without its loops plus every node's own: the pattern of a normalised
+    adjacency with self-loops, which GGCNlayer_SP's plain branch propagates over (diagonal kept)."""
+    ei = ei[:, ei[0] != ei[1]]
+    return torch.unique(torch.cat([ei, torch.arange(n).repeat(2, 1)], 1), dim=1)
+
+
+def oracle_signed_fixed(h, rowptr, col, coef, c2, sign, gout, row_offset=0, eps=1e-12):
+    """The signed attention from the oracle's own blocks in h's dtype, the sign of every edge FIXED: F.normalize,
+    O.edge_cosine, relu(s) / -relu(-s) (both 0 where ``sign`` is 0), index_add_ in edge order, autograd for the
+    gradients of <out, gout>.  Keys as arbiter.signed: out, s, grad, u, grad_coef, grad_c2."""
+    rowptr, col = torch.as_tensor(np.asarray(rowptr)).long(), torch.as_tensor(np.asarray(col)).long()
+    n = rowptr.numel() - 1
+    dst = torch.repeat_interleave(torch.arange(n), rowptr.diff())
+    live = torch.as_tensor(np.asarray(sign)).long() != 0
+    h = h.detach().clone().requires_grad_(True)
+    coef = torch.as_tensor(coef).detach().to(h.dtype).clone().requires_grad_(True)
+    c2 = torch.as_tensor(c2).detach().to(h.dtype).clone().requires_grad_(True)
+    gout = gout.to(h.dtype)
+    s = O.edge_cosine(torch.nn.functional.normalize(h, p=2., dim=-1, eps=eps), torch.stack([col, dst + row_offset]))
+    zero = torch.zeros_like(s)
+    e_pos = torch.where(live, torch.relu(s), zero)
+    e_neg = torch.where(live, -torch.relu(-s), zero)
+    hj = h.index_select(0, col)
+    out = torch.zeros(n, h.size(1), dtype=h.dtype).index_add_(0, dst, (coef * (c2[0] * e_pos + c2[1] * e_neg)).view(-1, 1) * hj)
+    (out * gout).sum().backward()
+    with torch.no_grad():
+        u = s * (gout.index_select(0, dst) * hj).sum(-1)
+    return dict(out=out.detach(), s=s.detach(), grad=h.grad, u=u, grad_coef=coef.grad, grad_c2=c2.grad)
+
+
+def oracle_weighted(x, rowptr, col, w, gout, n_total=None):
+    """torch.sparse.mm autograd in x's dtype on a CSR's pattern: dict(out, grad_x, grad_w [E] in CSR order)."""
+    rowptr, col = torch.as_tensor(np.asarray(rowptr)).long(), torch.as_tensor(np.asarray(col)).long()
+    n = rowptr.numel() - 1
+    dst = torch.repeat_interleave(torch.arange(n), rowptr.diff())
+    x = x.detach().clone().requires_grad_(True)
+    w = w.detach().to(x.dtype).clone().requires_grad_(True)
+    a = torch.sparse_coo_tensor(torch.stack([dst, col]), w, (n, x.size(0)))
+    out = torch.sparse.mm(a, x)
+    (out * gout.to(x.dtype)).sum().backward()
+    return dict(out=out.detach(), grad_x=x.grad, grad_w=w.grad)
+
+
 REGIME_HUB_SOURCE = 4
 REGIME_ISOLATED = 50
 
@@ -120,6 +223,49 @@ def oracle_fixed_mask(h, rowptr, col, kept, gout, row_offset=0):
     out = O.scatter_mean(w.view(-1, 1) * h.index_select(0, col), dst, n)
     (out * gout.to(h.dtype)).sum().backward()
     return out.detach(), h.grad
+
+
+def ggcn_scalar_gradients64(ref, adj, dp, h, gout):
+    """Float64 gradient AND magnitude of every scalar parameter (``coeff``, ``scale``, ``deg_coeff``) of the oracle
+    layer ``ref`` (O.GGCNlayer_SP, any dtype) for the loss <out, gout>: (values, magnitudes), dicts by parameter name.
+    The float64 arbiter's per-edge / per-coefficient results at F.cosine_similarity's eps = 1e-8 with G = scale x gout,
+    chained as autograd writes it - the softmax c_k (g_k - sum_m c_m g_m) (magnitude c_k (M_k + sum_m c_m M_m)), the
+    softplus' sigmoid, the degree scaling a_e = adj_e softplus(d_0 dv_e + d_1) - with absolute values throughout for
+    the magnitude.  No dense or sparse-times-sparse intermediate: lean at any graph size."""
+    from tests import arbiter
+    idx, val = adj._indices(), adj._values().double()
+    n = adj.size(0)
+    p = {k: v.detach().double() for k, v in ref.named_parameters()}
+    wh = h.double() @ p["fcn.weight"].t() + p["fcn.bias"]
+    g = gout.double()
+    coef, vals, mags = val, {}, {}
+    if ref.use_degree:
+        dv = dp._values().double()
+        z = p["deg_coeff"][0] * dv + p["deg_coeff"][1]
+        coef, sig = val * torch.nn.functional.softplus(z), torch.sigmoid(z)
+    keep = idx[0] != idx[1] if ref.use_sign else torch.ones_like(idx[0], dtype=torch.bool)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64)
+    rowptr[1:] = torch.cumsum(torch.bincount(idx[0][keep], minlength=n), 0)              # coalesced: sorted by row
+    if ref.use_sign:
+        c, scale = torch.softmax(p["coeff"], -1), torch.nn.functional.softplus(p["scale"])[0]
+        pos, neg = O.signed_attention_values(idx[:, keep], wh)
+        arb = arbiter.signed(rowptr, idx[1][keep], wh, coef[keep], c[:2], torch.sign(pos + neg).long(), scale * g,
+                             eps=1e-8, routes=False)
+        gw, GW = (g * wh).sum(), (g.abs() * wh.abs()).sum()
+        gc, mc = torch.cat([arb["grad_c2"], (scale * gw).view(1)]), torch.cat([arb["MAG_grad_c2"], (scale * GW).view(1)])
+        vals["coeff"], mags["coeff"] = c * (gc - (c * gc).sum()), c * (mc + (c * mc).sum())
+        dsp = torch.sigmoid(p["scale"])
+        vals["scale"] = dsp * ((g * arb["out"]).sum() + c[2] * gw)
+        mags["scale"] = dsp * ((g.abs() * arb["MAG_out"]).sum() + c[2] * GW)
+        g_coef, m_coef = arb["grad_coef"], arb["MAG_grad_coef"]
+    else:
+        arb = arbiter.weighted(rowptr, idx[1], coef, wh, g)
+        g_coef, m_coef = arb["grad_w"], arb["MAG_grad_w"]
+    if ref.use_degree:
+        va, sg, dk = val[keep], sig[keep], dv[keep]
+        vals["deg_coeff"] = torch.stack([(g_coef * va * sg * dk).sum(), (g_coef * va * sg).sum()])
+        mags["deg_coeff"] = torch.stack([(m_coef * va.abs() * sg * dk.abs()).sum(), (m_coef * va.abs() * sg).sum()])
+    return vals, mags
 
 
 def row_classes(rowptr, h, row_offset=0, loops_kept=False):

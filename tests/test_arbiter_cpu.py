@@ -5,7 +5,8 @@ import torch
 
 from oracle import sngnn_oracle as O
 from tests import arbiter, helpers
-from tests.helpers import REGIMES, csr_of_edge_list, oracle_fixed_mask, regime_edges, regime_inputs
+from tests.helpers import (REGIMES, SIGNED_REGIMES, csr_of_edge_list, oracle_fixed_mask, oracle_signed_fixed,
+                           oracle_weighted, regime_edges, regime_inputs, signed_inputs)
 
 N = 3000
 SELECTIONS = ((16, 0.0), (3, 0.3), (None, 0.0))
@@ -20,6 +21,9 @@ EQUAL = 1e-13          # arbiter == float64 autograd, in units of the magnitude 
 #                softmax denominator and weighted sum are sequential sums of 3000 terms; grad_h 77.1 / 66.0 on SMALL
 #                rows that are sources of the hub row - their message term alpha_e gout_0 inherits the relative error of
 #                that denominator.  On the same graph without the rows of more than 128 in-edges: out <= 16.4, grad_h <= 18.3.
+#   signed       (sign fixed, signed a_e: the hub row's terms do not share a sign) every output <= 7.5; the cosine itself
+#                <= 5.22 units of S_e; grad_c2, one sum over every edge, 0.26 at most (its errors average out);
+#   weighted     fp32 torch.sparse.mm autograd <= 7.74.
 # The attention magnitude deliberately does not price the denominator's length (it would loosen the gate for
 # kernels that do not sum that way), so on the full graph the attention K_ref - and with it the GPU gate,
 # 4 x K_ref - is that of a sequential sum, far wider than an fp32 rounding gate in ``parallel``, ``tiny`` and
@@ -28,7 +32,9 @@ EQUAL = 1e-13          # arbiter == float64 autograd, in units of the magnitude 
 SLACK = 1.5
 MEASURED = {"aggregation grad_h": 13.64, "aggregation out": 34.62, "aggregation out, rows <= 128": 11.66,
             "attention out": 347.68, "attention grad_h": 77.14,
-            "attention out, rows <= 128": 16.4, "attention grad_h, rows <= 128": 18.3}
+            "attention out, rows <= 128": 16.4, "attention grad_h, rows <= 128": 18.3,
+            "signed out": 7.50, "signed s": 5.22, "signed grad_h": 7.11, "signed u": 5.66, "signed grad_coef": 6.11,
+            "signed grad_c2": 0.26, "weighted out": 7.74, "weighted grad_x": 5.00, "weighted grad_w": 4.36}
 
 
 @pytest.fixture(scope="module")
@@ -106,6 +112,129 @@ def test_attention_arbiter_equals_float64_autograd(edges, kind):
     _report_and_bound("attention", kind, worst)
 
 
+SIGNED_OUTPUTS = (("out", "out"), ("s", "s"), ("grad_h", "grad"), ("u", "u"), ("grad_coef", "grad_coef"), ("grad_c2", "grad_c2"))
+SIGN_BAND_CAP = 1e-3   # share of the edges allowed inside the sign band
+
+
+def _signed_csr(edges):
+    return csr_of_edge_list(O.sn_edge_list(edges, N, False, True), N)[:2]
+
+
+@pytest.mark.parametrize("kind", SIGNED_REGIMES)
+def test_signed_arbiter_equals_float64_autograd(edges, kind):
+    """arbiter.signed with sign = sign(s64): every output within 1e-13 x MAG of float64 autograd through
+    oracle_signed_fixed; the fp32 oracle_signed_fixed in units of 2^-24 x MAG (K_ref, exactly 0 where MAG == 0);
+    and the sign band: the edges with 0 < |s64| <= gate(K_ref of s) 2^-24 S_e - the only ones on which an fp32
+    evaluation may take another branch of kappa - are at most 0.1 % of the edges."""
+    rowptr, col = _signed_csr(edges)
+    worst, band_worst = {}, 0
+    for c in (7, 40, 47, 130):
+        h, gout, coef_of, cases = signed_inputs(N, c, kind)
+        coef = coef_of(col.numel())
+        if kind == "lattice":
+            helpers.assert_lattice_share(h, rowptr, col)
+        for c2 in cases:
+            c2 = torch.tensor(c2)
+            sign = torch.sign(arbiter.signed(rowptr, col, h, coef, c2, torch.zeros(col.numel(), dtype=torch.int64))["s"]).long()
+            arb = arbiter.signed(rowptr, col, h, coef, c2, sign, gout)
+            r64 = oracle_signed_fixed(h.double(), rowptr, col, coef, c2, sign, gout)
+            r32 = oracle_signed_fixed(h, rowptr, col, coef, c2, sign, gout)
+            what = f"{kind} C={c} c2={tuple(c2.tolist())} signed"
+            e, ks = 0.0, {}
+            for name, key in SIGNED_OUTPUTS:
+                e = max(e, _assert_equal64(arb[key], r64[key], arb["MAG_" + key], f"{what} {name}"))
+                ks[name], _ = arbiter.reference_units(r32[key], arb[key], arb["MAG_" + key], f"{what} {name}")
+                worst[name] = max(worst.get(name, 0.0), ks[name])
+            band = arbiter.gate_units(ks["s"]) * arbiter.UNIT * arb["MAG_s"]
+            inside = int(((arb["s"] != 0) & (arb["s"].abs() <= band)).sum())
+            band_worst = max(band_worst, inside)
+            assert inside <= SIGN_BAND_CAP * col.numel(), f"{what}: {inside} of {col.numel()} edges inside the sign band"
+            print(f"{what}: arbiter vs float64 autograd {e:.1e} x MAG; fp32 oracle worst element, units of 2^-24 x MAG: "
+                  + " ".join(f"{k} {v:.2f}" for k, v in ks.items()) + f"; edges with sign +/0/-: {int((sign > 0).sum())}/"
+                  f"{int((sign == 0).sum())}/{int((sign < 0).sum())}, s == 0 with S > 0: "
+                  f"{int(((sign == 0) & (arb['MAG_s'] > 0)).sum())}; inside the sign band: {inside}")
+    helpers.REPORT_LINES.append(f"arbiter (CPU) signed {kind}: at most {band_worst} edges inside the sign band")
+    _report_and_bound("signed", kind, worst)
+
+
+def test_signed_arbiter_has_the_oracle_layers_semantics(edges):
+    """With eps = 1e-8 the arbiter is float64 autograd through O.signed_attention_values and the two
+    torch.sparse.mm of O.GGCNlayer_SP - on rows without a norm in (0, 1e-8), where F.cosine_similarity's clamp and
+    F.normalize's 1e-12 (the kernels', signed_impl.h) differ: ``near_eps`` has such rows, so the GPU tests run at 1e-12."""
+    rowptr, col = _signed_csr(edges)
+    dst = torch.repeat_interleave(torch.arange(N), rowptr.diff())
+    idx, c = torch.stack([dst, col]), 40
+    nrm = regime_inputs(N, c, "near_eps")[0].double().norm(dim=1)
+    assert int(((nrm > 0) & (nrm < 1e-8)).sum()) > 1000
+    for kind in ("normal", "sparse", "tiny", "antiparallel", "lattice"):
+        h, gout, coef_of, cases = signed_inputs(N, c, kind)
+        nrm = h.double().norm(dim=1)
+        assert not bool(((nrm > 0) & (nrm < 1e-8)).any())
+        c2 = torch.tensor(cases[0])
+        wh = h.double().requires_grad_(True)
+        a = coef_of(col.numel()).double().requires_grad_(True)
+        k = c2.double().requires_grad_(True)
+        pos, neg = O.signed_attention_values(idx, wh)
+        prop = [torch.sparse.mm(torch.sparse_coo_tensor(idx, a * e, (N, N)), wh) for e in (pos, neg)]
+        out = k[0] * prop[0] + k[1] * prop[1]
+        (out * gout.double()).sum().backward()
+        s64 = (pos + neg).detach()
+        arb = arbiter.signed(rowptr, col, h, a.detach(), c2, torch.sign(s64).long(), gout, eps=1e-8)
+        for name, got, key in (("out", out.detach(), "out"), ("s", s64, "s"), ("grad_h", wh.grad, "grad"),
+                               ("grad_coef", a.grad, "grad_coef"), ("grad_c2", k.grad, "grad_c2")):
+            _assert_equal64(arb[key], got, arb["MAG_" + key], f"{kind} oracle layer semantics {name}")
+
+
+@pytest.mark.parametrize("kind", REGIMES)
+def test_weighted_arbiter_equals_float64_autograd(edges, kind):
+    """arbiter.weighted against float64 autograd of torch.sparse.mm on the pattern with the diagonal kept, and the
+    fp32 torch.sparse.mm in the arbiter's units."""
+    rowptr, col, _ = csr_of_edge_list(helpers.adj_with_diagonal(edges, N), N)
+    worst = {}
+    for c in (5, 40, 130):
+        x, gout, coef_of, _ = signed_inputs(N, c, kind)
+        w = coef_of(col.numel())
+        arb = arbiter.weighted(rowptr, col, w, x, gout)
+        r64, r32 = oracle_weighted(x.double(), rowptr, col, w, gout), oracle_weighted(x, rowptr, col, w, gout)
+        ks = {}
+        for key in ("out", "grad_x", "grad_w"):
+            _assert_equal64(arb[key], r64[key], arb["MAG_" + key], f"{kind} C={c} weighted {key}")
+            ks[key], _ = arbiter.reference_units(r32[key], arb[key], arb["MAG_" + key], f"{kind} C={c} weighted {key}")
+            worst[key] = max(worst.get(key, 0.0), ks[key])
+        print(f"{kind} C={c} weighted: fp32 torch.sparse.mm worst element, units of 2^-24 x MAG: "
+              + " ".join(f"{k} {v:.2f}" for k, v in ks.items()))
+    _report_and_bound("weighted", kind, worst)
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(use_degree=False), dict(use_decay=False), dict(use_sign=False)])
+def test_layer_scalar_gradients_equal_float64_autograd(kw):
+    """helpers.ggcn_scalar_gradients64 - what prices ``coeff``, ``scale`` and ``deg_coeff`` in tests/test_ggcn_gpu.py -
+    against float64 autograd through O.GGCNlayer_SP itself, within 1e-13 x its own magnitude."""
+    n, f, c = 300, 9, 7
+    ei = helpers.adj_with_diagonal(helpers.random_graph(n, 1500, seed=2, hubs=((3, 200),)), n)
+    sym = torch.unique(torch.cat([ei, ei.flip(0)], 1), dim=1)
+    deg = torch.bincount(sym[1], minlength=n).double()
+    adj = torch.sparse_coo_tensor(sym.flip(0), (1.0 / torch.sqrt(deg[sym[0]] * deg[sym[1]])).float(), (n, n)).coalesce()
+    dp = O.ggcn_degree_precompute(adj)
+    torch.manual_seed(4)
+    ref = O.GGCNlayer_SP(f, c, "cpu", **kw)
+    with torch.no_grad():
+        if ref.use_sign:
+            ref.coeff.copy_(torch.tensor([0.5, -0.3, 0.2]))
+        if ref.use_degree:
+            ref.deg_coeff.copy_(torch.tensor([0.4, -0.1]))
+    h, gout = torch.randn(n, f), torch.randn(n, c)
+    vals, mags = helpers.ggcn_scalar_gradients64(ref, adj, dp, h, gout)
+    ref64 = ref.double()
+    (ref64(h.double(), adj.double(), dp.double()) * gout.double()).sum().backward()
+    names = [k for k, _ in ref64.named_parameters() if not k.startswith("fcn")]
+    assert sorted(names) == sorted(vals) and names
+    for k, q in ref64.named_parameters():
+        if k in vals:
+            _assert_equal64(vals[k], q.grad, mags[k], f"{kw} {k}")
+            assert bool((mags[k] >= q.grad.abs()).all())
+
+
 def _report_and_bound(op, kind, worst):
     helpers.REPORT_LINES.append(f"arbiter (CPU) {op} {kind}: fp32 oracle worst element, units of 2^-24 x MAG: "
                                 + ", ".join(f"{key} {v:.2f}" for key, v in worst.items()))
@@ -131,3 +260,18 @@ def test_partition_rows_and_clamp():
     assert bool(((tot - whole["grad"]).abs() <= 1e-14 * mag).all())
     assert bool(((mag - whole["MAG_grad"]).abs() <= 1e-14 * mag).all())
     assert bool((h.double().norm(dim=1) < 1e-12).any())
+    # the signed attention: per-edge s and u of the owned rows as well
+    coef, c2 = helpers.signed_coef(col.numel(), 3), torch.tensor(helpers.SIGNED_C2[0])
+    sign = torch.sign(arbiter.signed(rowptr, col, h, coef, c2, torch.zeros(col.numel(), dtype=torch.int64))["s"]).long()
+    assert bool((sign > 0).any()) and bool((sign < 0).any())
+    whole = arbiter.signed(rowptr, col, h, coef, c2, sign, gout)
+    tot, mag = torch.zeros_like(whole["grad"]), torch.zeros_like(whole["grad"])
+    for lo, hi in ((0, 25), (25, 60)):
+        e0, e1 = int(rowptr[lo]), int(rowptr[hi])
+        p = arbiter.signed(rowptr[lo:hi + 1] - rowptr[lo], col[e0:e1], h, coef[e0:e1], c2, sign[e0:e1], gout[lo:hi], row_offset=lo)
+        assert torch.equal(p["out"], whole["out"][lo:hi])
+        for key in ("s", "u", "grad_coef", "MAG_s", "MAG_u"):
+            assert torch.equal(p[key], whole[key][e0:e1]), key
+        tot, mag = tot + p["grad"], mag + p["MAG_grad"]
+    assert bool(((tot - whole["grad"]).abs() <= 1e-14 * mag).all())
+    assert bool(((mag - whole["MAG_grad"]).abs() <= 1e-14 * mag).all())
