@@ -416,7 +416,42 @@ int sngnn_signed_backward(const sngnn_graph_t *g, const float *wh, int C, const 
                           void *workspace, void *stream);
 
 /*
- * Replaces: the SNGNN++ blend  out = beta * out_0 + (1 - beta) * out_1  (models.py:134)
+ * Half-width feature rows in the two attention modes: cosine attention and signed cosine attention on fp16 or
+ * bf16 rows, forward and backward.
+ * Replaces the same reference lines as the fp32 entries above (AGNNConv, models.py:396-405; GGCNlayer_SP's
+ * use_sign branch, models.py:1512-1519 + :1529-1537; autograd through them) for a model cast to torch.float16 /
+ * torch.bfloat16 - but NOT their eager arithmetic in that type: norms, cosines, exp, softmax sums and every
+ * accumulation stay fp32.  Contract, with hf / whf = the rows widened to fp32 and gf = grad_out widened (exact):
+ *   attention forward:  out == sngnn_attn_forward(hf).out rounded once to the storage type (round to nearest
+ *                       even); alpha stays fp32 and equals that call's alpha bit for bit.
+ *   attention backward: grad_h == sngnn_attn_backward(hf, gf, alpha) rounded once.
+ *   signed forward:     out == sngnn_signed_forward(whf, coef, c2).out rounded once; s stays fp32 and equals that
+ *                       call's s bit for bit, so every edge's sign and kappa are the fp32 call's.
+ *   signed backward:    grad_wh == sngnn_signed_backward(whf, gf, coef, s, c2).grad_wh rounded once; u stays fp32
+ *                       and equals that call's u bit for bit.
+ * The kernels are the fp32 ones with their row loads and output stores in the storage type: same lanes, same
+ * summation order.  coef, c2, alpha, s, u, the task partials, dnT / partT / partS / rec_dot and the per-edge records
+ * are fp32 in the fp32 entries' workspace layout; a split row's out is the fp32 total (divided by l in the
+ * attention mode) rounded once.  Deterministic, no floating-point atomics, no host synchronisation.
+ *   dtype    SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16: the type of h / wh, out, grad_out and grad_h / grad_wh (anything
+ *            else: SNGNN_EINVAL with "dtype" in sngnn_last_error(), before the graph or any pointer is looked at)
+ *   h, wh, out, grad_out, grad_h, grad_wh   dev, that type, rows of C values aligned to 2 * vec bytes (vec = 4, 2
+ *            or 1 for C % 4 == 0, C % 2 == 0, odd C: the fp32 layout's values per lane)
+ *   workspace  sngnn_graph_workspace_bytes(g, C) bytes (an upper bound, as for the fp32 entries)
+ * Everything else as in sngnn_attn_forward / sngnn_attn_backward / sngnn_signed_forward / sngnn_signed_backward.
+ */
+int sngnn_attn_forward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, void *out,
+                            float *alpha, void *workspace, void *stream);
+int sngnn_attn_backward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, const void *grad_out,
+                             const float *alpha, void *grad_h, void *workspace, void *stream);
+int sngnn_signed_forward_half(const sngnn_graph_t *g, const void *wh, int dtype, int C, const float *coef,
+                              const float *c2, void *out, float *s, void *workspace, void *stream);
+int sngnn_signed_backward_half(const sngnn_graph_t *g, const void *wh, int dtype, int C, const void *grad_out,
+                               const float *coef, const float *s, const float *c2, void *grad_wh, float *u,
+                               void *workspace, void *stream);
+
+/*
+ * Replaces: the SNGNN++ blend out = beta * out_0 + (1 - beta) * out_1  (models.py:134)
  * and its autograd, one pass over the n = N * C elements each way instead of five
  * elementwise launches.  beta: dev f32 [1] (the layer's Parameter).  Backward writes
  * grad0 = beta * grad_out, grad1 = (1 - beta) * grad_out and grad_beta [1] =

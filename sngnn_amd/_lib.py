@@ -71,6 +71,10 @@ SIGNATURES = {
     "sngnn_attn_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_signed_forward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_signed_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_attn_forward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_attn_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_signed_forward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_signed_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_blend_workspace_bytes": (_i64, []),
     "sngnn_blend_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_blend_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),

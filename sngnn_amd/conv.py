@@ -332,6 +332,16 @@ class AGNNConv(nn.Module):
         self.lin.reset_parameters()
 
     def forward(self, x, edge_index):
+        if x.dtype in ops.HALF_DTYPES:
+            # the half path (see HALF_PAD's note): ``lin`` is torch's F.linear, the attention the library's half
+            # kernels - the fp32 operator on h.float(), only its output rounded to the type
+            graph, _ = _graph_for(x, edge_index, True, LOOPS_REPLACE)       # (a partition refuses half features)
+            c = self.lin.out_features
+            weight, bias, cp = self.lin.weight, self.lin.bias, half_width(c)
+            if cp != c:
+                weight = F.pad(weight, (0, 0, 0, cp - c))
+                bias = None if bias is None else F.pad(bias, (0, cp - c))
+            return _true_width(ops.attention(F.linear(x, weight, bias), graph), c)
         graph, shard = _graph_for(x, edge_index, True, LOOPS_REPLACE)
         h, c, table = _lin_aligned(x, self.lin, shard)
         if shard is not None:

@@ -3,25 +3,27 @@
 
 using namespace sngnn;
 
-static int check_rows(int C, RowCfg &cfg, const void *p0, const void *p1, const void *p2)
+// dtype: 0 = fp32 rows, else SNGNN_DTYPE_F16 / SNGNN_DTYPE_BF16 (2 bytes a value)
+static int check_rows(int C, RowCfg &cfg, const void *p0, const void *p1, const void *p2, int dtype)
 {
     SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL,
                "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    const uintptr_t al = (uintptr_t)cfg.vec * 4;
+    const uintptr_t al = (uintptr_t)cfg.vec * (dtype != 0 ? 2 : 4);
     SN_REQUIRE((uintptr_t)p0 % al == 0 && (uintptr_t)p1 % al == 0 && (uintptr_t)p2 % al == 0,
                SNGNN_EINVAL, "feature tables must be aligned to the row vector width");
     return SNGNN_OK;
 }
 
-extern "C" int sngnn_attn_forward(const sngnn_graph_t *g, const float *h, int C, float *out,
-                                  float *alpha, void *workspace, void *stream)
+// h and out are float rows for dtype 0, else rows of the half type behind the same pointers
+static int forward_impl(const sngnn_graph_t *g, const float *h, int dtype, int C, float *out, float *alpha,
+                        void *workspace, void *stream)
 {
     SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
     if (g->N == 0) return SNGNN_OK;
     SN_REQUIRE(h && out, SNGNN_EINVAL, "NULL argument");
     SN_REQUIRE(workspace != nullptr || g->n_tasks == 0, SNGNN_EINVAL, "workspace is NULL");
     RowCfg cfg;
-    if (int rc = check_rows(C, cfg, h, out, nullptr)) return rc;
+    if (int rc = check_rows(C, cfg, h, out, nullptr, dtype)) return rc;
     AttnArgs a;
     a.h = h; a.C = C; a.N = (int)g->N; a.row_off = (int)g->row_off;
     a.col = g->col; a.rdesc = g->rdesc;
@@ -31,6 +33,14 @@ extern "C" int sngnn_attn_forward(const sngnn_graph_t *g, const float *h, int C,
     a.partial = (float *)workspace;     // [n_tasks][C + 4] <= the forward workspace of the graph
     a.nbA = a.nbB = 0;
     hipStream_t st = (hipStream_t)stream;
+    if (dtype != 0) {
+        const bool f16 = dtype == SNGNN_DTYPE_F16;
+        switch (cfg.vec) {
+        case 1: return f16 ? launch_attn_fwd_f16_v1(cfg, a, st) : launch_attn_fwd_bf16_v1(cfg, a, st);
+        case 2: return f16 ? launch_attn_fwd_f16_v2(cfg, a, st) : launch_attn_fwd_bf16_v2(cfg, a, st);
+        default: return f16 ? launch_attn_fwd_f16_v4(cfg, a, st) : launch_attn_fwd_bf16_v4(cfg, a, st);
+        }
+    }
     switch (cfg.vec) {
     case 1: return launch_attn_fwd_v1(cfg, a, st);
     case 2: return launch_attn_fwd_v2(cfg, a, st);
@@ -38,16 +48,30 @@ extern "C" int sngnn_attn_forward(const sngnn_graph_t *g, const float *h, int C,
     }
 }
 
-extern "C" int sngnn_attn_backward(const sngnn_graph_t *g, const float *h, int C,
-                                   const float *grad_out, const float *alpha, float *grad_h,
-                                   void *workspace, void *stream)
+extern "C" int sngnn_attn_forward(const sngnn_graph_t *g, const float *h, int C, float *out,
+                                  float *alpha, void *workspace, void *stream)
+{
+    return forward_impl(g, h, 0, C, out, alpha, workspace, stream);
+}
+
+// the half path: h and out stored as fp16 / bf16 (alpha and the workspace as in sngnn_attn_forward)
+extern "C" int sngnn_attn_forward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, void *out,
+                                       float *alpha, void *workspace, void *stream)
+{
+    SN_REQUIRE(dtype == SNGNN_DTYPE_F16 || dtype == SNGNN_DTYPE_BF16, SNGNN_EINVAL,
+               "dtype must be SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16");
+    return forward_impl(g, (const float *)h, dtype, C, (float *)out, alpha, workspace, stream);
+}
+
+static int backward_impl(const sngnn_graph_t *g, const float *h, int dtype, int C, const float *grad_out,
+                         const float *alpha, float *grad_h, void *workspace, void *stream)
 {
     SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
     if (g->Ntot == 0) return SNGNN_OK;
     SN_REQUIRE(h && grad_h && workspace && (grad_out || g->N == 0), SNGNN_EINVAL, "NULL argument");
     SN_REQUIRE(alpha != nullptr || g->Ep == 0, SNGNN_EINVAL, "alpha is NULL");
     RowCfg cfg;
-    if (int rc = check_rows(C, cfg, h, grad_out, grad_h)) return rc;
+    if (int rc = check_rows(C, cfg, h, grad_out, grad_h, dtype)) return rc;
     BwdArgs a;
     a.h = h; a.gout = grad_out; a.wsel = alpha;
     a.C = C; a.N = (int)g->N; a.Ntot = (int)g->Ntot; a.row_off = (int)g->row_off;
@@ -73,9 +97,34 @@ extern "C" int sngnn_attn_backward(const sngnn_graph_t *g, const float *h, int C
     a.fdesc = nullptr; a.trest = nullptr; a.n_fused = a.n_trest = 0;
     a.kbits = nullptr; a.csc_bit = nullptr; a.kb_wbase = a.kb_tbase = 0;
     hipStream_t st = (hipStream_t)stream;
+    if (dtype != 0) {
+        const bool f16 = dtype == SNGNN_DTYPE_F16;
+        switch (cfg.vec) {
+        case 1: return f16 ? launch_attn_bwd_f16_v1(cfg, a, st) : launch_attn_bwd_bf16_v1(cfg, a, st);
+        case 2: return f16 ? launch_attn_bwd_f16_v2(cfg, a, st) : launch_attn_bwd_bf16_v2(cfg, a, st);
+        default: return f16 ? launch_attn_bwd_f16_v4(cfg, a, st) : launch_attn_bwd_bf16_v4(cfg, a, st);
+        }
+    }
     switch (cfg.vec) {
     case 1: return launch_attn_bwd_v1(cfg, a, st);
     case 2: return launch_attn_bwd_v2(cfg, a, st);
     default: return launch_attn_bwd_v4(cfg, a, st);
     }
+}
+
+extern "C" int sngnn_attn_backward(const sngnn_graph_t *g, const float *h, int C,
+                                   const float *grad_out, const float *alpha, float *grad_h,
+                                   void *workspace, void *stream)
+{
+    return backward_impl(g, h, 0, C, grad_out, alpha, grad_h, workspace, stream);
+}
+
+// the half path: h, grad_out and grad_h stored as fp16 / bf16 (alpha, the records and every scratch row stay fp32)
+extern "C" int sngnn_attn_backward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, const void *grad_out,
+                                        const float *alpha, void *grad_h, void *workspace, void *stream)
+{
+    SN_REQUIRE(dtype == SNGNN_DTYPE_F16 || dtype == SNGNN_DTYPE_BF16, SNGNN_EINVAL,
+               "dtype must be SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16");
+    return backward_impl(g, (const float *)h, dtype, C, (const float *)grad_out, alpha, (float *)grad_h, workspace,
+                         stream);
 }

@@ -33,12 +33,22 @@ struct AttnArgs {
     const int32_t *task_slot, *task_chunk, *split_task0;
     float *partial;              // [n_tasks][C + 4]: weighted row sum | l, 0, 0, 0
     int nbA, nbB;
+    // h and out in their storage type S (the kernels' template parameter): float, or __half / __hip_bfloat16 for
+    // the half path (sngnn_attn_forward_half).  alpha and the task partials stay fp32.
+    template <typename S> __device__ __forceinline__ const S *rows() const { return reinterpret_cast<const S *>(h); }
+    template <typename S> __device__ __forceinline__ S *outs() const { return reinterpret_cast<S *>(out); }
+    // one value of out: `a.out_at<S>(idx) = v` (float: the plain element itself; else v rounded to S)
+    template <typename S> __device__ __forceinline__ decltype(auto) out_at(size_t idx) const
+    {
+        if constexpr (std::is_same<S, float>::value) return (out[idx]);
+        else return HalfRef<S>{outs<S>() + idx};
+    }
 };
 
 constexpr int ATTN_LDS = 2 * WAVE_T;    // words per wave: source ids | exp(s) (or t_e)
 
 // ------------------------------ forward ------------------------------------
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void attn_small(const AttnArgs &a, int blk, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -53,7 +63,7 @@ __device__ __forceinline__ void attn_small(const AttnArgs &a, int blk, int *lds_
     float *s_e = reinterpret_cast<float *>(s_j + SMALL_T);
     for (int t = lg; t < deg; t += G) s_j[t] = a.col[rs + t];
     RowT hi, acc;
-    hi.load(a.h + (size_t)(a.row_off + i) * a.C, a.C, lg);
+    hi.load(a.rows<S>() + (size_t)(a.row_off + i) * a.C, a.C, lg);
     const float inv_i = inv_norm_of(group_sum<G>(hi.dot_partial(hi)));
     acc.zero();
     float l = 0.f;
@@ -61,8 +71,8 @@ __device__ __forceinline__ void attn_small(const AttnArgs &a, int blk, int *lds_
     for (int t0 = 0; t0 < deg; t0 += 2) {
         const bool two = t0 + 1 < deg;
         RowT x0, x1;
-        x0.load(a.h + (size_t)s_j[t0] * a.C, a.C, lg);
-        if (two) x1.load(a.h + (size_t)s_j[t0 + 1] * a.C, a.C, lg);
+        x0.load(a.rows<S>() + (size_t)s_j[t0] * a.C, a.C, lg);
+        if (two) x1.load(a.rows<S>() + (size_t)s_j[t0 + 1] * a.C, a.C, lg);
         const float e0 = expf(edge_score<VEC, G, R>(hi, inv_i, x0));
         l += e0;
         fma_row<VEC, G, R>(acc, e0, x0);
@@ -75,14 +85,14 @@ __device__ __forceinline__ void attn_small(const AttnArgs &a, int blk, int *lds_
         }
     }
     if (deg > 0) acc.div(l);
-    acc.store(a.out + (size_t)i * a.C, a.C, lg);
+    acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     if (a.alpha) {
         wave_lds_sync();
         for (int t = lg; t < deg; t += G) a.alpha[rs + t] = s_e[t] / l;
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void attn_wave(const AttnArgs &a, int blk, int *lds_wave, bool task)
 {
     using RowT = Row<VEC, G, R>;
@@ -106,7 +116,7 @@ __device__ __forceinline__ void attn_wave(const AttnArgs &a, int blk, int *lds_w
     float *s_e = reinterpret_cast<float *>(lds_wave + WAVE_T);
     for (int t = lane; t < n; t += 64) s_j[t] = a.col[rs + e0 + t];
     RowT hi, acc;
-    hi.load(a.h + (size_t)(a.row_off + i) * a.C, a.C, lg);
+    hi.load(a.rows<S>() + (size_t)(a.row_off + i) * a.C, a.C, lg);
     const float inv_i = inv_norm_of(group_sum<G>(hi.dot_partial(hi)));
     acc.zero();
     float l = 0.f;
@@ -115,7 +125,7 @@ __device__ __forceinline__ void attn_wave(const AttnArgs &a, int blk, int *lds_w
         const int q = q0 + gid;
         if (q < n) {
             RowT x;
-            x.load(a.h + (size_t)s_j[q] * a.C, a.C, lg);
+            x.load(a.rows<S>() + (size_t)s_j[q] * a.C, a.C, lg);
             const float e = expf(edge_score<VEC, G, R>(hi, inv_i, x));
             l += e;
             fma_row<VEC, G, R>(acc, e, x);
@@ -136,21 +146,21 @@ __device__ __forceinline__ void attn_wave(const AttnArgs &a, int blk, int *lds_w
             for (int t = lane; t < n; t += 64) a.alpha[rs + e0 + t] = s_e[t];
     } else {
         acc.div(l);
-        if (gid == 0) acc.store(a.out + (size_t)i * a.C, a.C, lg);
+        if (gid == 0) acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
         if (a.alpha)
             for (int t = lane; t < n; t += 64) a.alpha[rs + t] = s_e[t] / l;
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_attn_fwd(const AttnArgs a)
 {
     __shared__ int lds[WAVES][ATTN_LDS];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
-    if (b < a.nbA) attn_wave<VEC, G, R>(a, b, lw, true);
-    else if (b < a.nbA + a.nbB) attn_wave<VEC, G, R>(a, b - a.nbA, lw, false);
-    else attn_small<VEC, G, R>(a, b - a.nbA - a.nbB, lw);
+    if (b < a.nbA) attn_wave<VEC, G, R, S>(a, b, lw, true);
+    else if (b < a.nbA + a.nbB) attn_wave<VEC, G, R, S>(a, b - a.nbA, lw, false);
+    else attn_small<VEC, G, R, S>(a, b - a.nbA - a.nbB, lw);
 }
 
 // split rows: l_i and the weighted sum over the row's tasks (fixed order), then the
@@ -174,7 +184,8 @@ __device__ __forceinline__ float afin_block_sum(float v, float *s_red)
     return tot;
 }
 
-static __global__ __launch_bounds__(AFIN_BLOCK) void k_attn_fin(const AttnArgs a)
+// (S: out is stored in the storage type - the fp32 total divided by l, rounded once)
+template <typename S = float> __global__ __launch_bounds__(AFIN_BLOCK) void k_attn_fin(const AttnArgs a)
 {
     __shared__ float s[AFIN_WAVES][64];
     __shared__ float s_red[AFIN_WAVES];
@@ -198,7 +209,7 @@ static __global__ __launch_bounds__(AFIN_BLOCK) void k_attn_fin(const AttnArgs a
             float tot = 0.f;
 #pragma unroll
             for (int w = 0; w < AFIN_WAVES; ++w) tot += s[w][cl];
-            a.out[(size_t)i * a.C + c] = tot / l;
+            a.out_at<S>((size_t)i * a.C + c) = tot / l;
         }
         __syncthreads();
     }
@@ -221,15 +232,15 @@ static __global__ __launch_bounds__(AFIN_BLOCK) void k_attn_fin(const AttnArgs a
     }
 }
 
-template <int VEC, int G, int R> int launch_attn_fwd(const AttnArgs &a0, hipStream_t st)
+template <int VEC, int G, int R, typename S = float> int launch_attn_fwd(const AttnArgs &a0, hipStream_t st)
 {
     constexpr int RPW = 64 / G;
     AttnArgs a = a0;
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
     const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_attn_fwd<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_split > 0) k_attn_fin<<<a.n_split, AFIN_BLOCK, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_attn_fwd<VEC, G, R, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.n_split > 0) k_attn_fin<S><<<a.n_split, AFIN_BLOCK, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -253,7 +264,7 @@ __device__ __forceinline__ float attn_t_edge(const Row<VEC, G, R> &x, const Row<
     return t;
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void attn_t_small(const BwdArgs &a, int blk, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -273,7 +284,7 @@ __device__ __forceinline__ void attn_t_small(const BwdArgs &a, int blk, int *lds
         s_a[t] = a.wsel[rs + t];
     }
     RowT gp, A, B;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     A.zero();
     B.zero();
     float dot = 0.f;
@@ -281,8 +292,8 @@ __device__ __forceinline__ void attn_t_small(const BwdArgs &a, int blk, int *lds
     for (int t0 = 0; t0 < deg; t0 += 2) {
         const bool two = t0 + 1 < deg;
         RowT x0, x1;
-        x0.load(a.h + (size_t)s_j[t0] * a.C, a.C, lg);
-        if (two) x1.load(a.h + (size_t)s_j[t0 + 1] * a.C, a.C, lg);
+        x0.load(a.hrows<S>() + (size_t)s_j[t0] * a.C, a.C, lg);
+        if (two) x1.load(a.hrows<S>() + (size_t)s_j[t0 + 1] * a.C, a.C, lg);
         const float ta = attn_t_edge<VEC, G, R>(x0, gp, s_a[t0], A, B, dot);
         if (lg == 0) s_t[t0] = ta;
         if (two) {
@@ -296,7 +307,7 @@ __device__ __forceinline__ void attn_t_small(const BwdArgs &a, int blk, int *lds
     for (int t = lg; t < deg; t += G) a.wd[a.csc_pos[rs + t]] = make_float2(s_a[t], s_a[t] * (s_t[t] - dot));
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void attn_t_wave(const BwdArgs &a, int blk, int *lds_wave, bool task)
 {
     using RowT = Row<VEC, G, R>;
@@ -325,7 +336,7 @@ __device__ __forceinline__ void attn_t_wave(const BwdArgs &a, int blk, int *lds_
         s_a[t] = a.wsel[rs + e0 + t];
     }
     RowT gp, A, B;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     A.zero();
     B.zero();
     float dot = 0.f;
@@ -334,7 +345,7 @@ __device__ __forceinline__ void attn_t_wave(const BwdArgs &a, int blk, int *lds_
         const int q = q0 + gid;
         if (q < n) {
             RowT x;
-            x.load(a.h + (size_t)s_j[q] * a.C, a.C, lg);
+            x.load(a.hrows<S>() + (size_t)s_j[q] * a.C, a.C, lg);
             const float t = attn_t_edge<VEC, G, R>(x, gp, s_a[q], A, B, dot);
             if (lg == 0) s_t[q] = t;
         }
@@ -360,15 +371,15 @@ __device__ __forceinline__ void attn_t_wave(const BwdArgs &a, int blk, int *lds_
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_attn_bwd_t(const BwdArgs a)
 {
     __shared__ __align__(16) int lds[WAVES][3 * WAVE_T];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
-    if (b < a.nbA) attn_t_wave<VEC, G, R>(a, b, lw, true);
-    else if (b < a.nbA + a.nbB) attn_t_wave<VEC, G, R>(a, b - a.nbA, lw, false);
-    else attn_t_small<VEC, G, R>(a, b - a.nbA - a.nbB, lw);
+    if (b < a.nbA) attn_t_wave<VEC, G, R, S>(a, b, lw, true);
+    else if (b < a.nbA + a.nbB) attn_t_wave<VEC, G, R, S>(a, b - a.nbA, lw, false);
+    else attn_t_small<VEC, G, R, S>(a, b - a.nbA - a.nbB, lw);
 }
 
 // Split rows after the tasks: dnT_i and dot_i from the row's task partials, one workgroup per row, every step
@@ -416,21 +427,21 @@ static __global__ __launch_bounds__(BLOCK) void k_attn_bwd_t_fin(const BwdArgs a
     }
 }
 
-template <int VEC, int G, int R> int launch_attn_bwd(const BwdArgs &a0, hipStream_t st)
+template <int VEC, int G, int R, typename S = float> int launch_attn_bwd(const BwdArgs &a0, hipStream_t st)
 {
     constexpr int RPW = 64 / G;
     BwdArgs a = a0;
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
     int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_attn_bwd_t<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_attn_bwd_t<VEC, G, R, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_attn_bwd_t_fin<<<a.n_split, BLOCK, 0, st>>>(a);
     // pass S: the aggregation's kernels (every edge kept, weight alpha_e, no mean division)
     a.nbA = ceil_div(a.n_stasks, WAVES);
     a.nbB = ceil_div(a.n_smed_end - a.n_ssplit, WAVES);
     nbC = ceil_div(a.Ntot - a.n_smed_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, true><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R><<<a.n_ssplit, 64, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, true, false, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R, S><<<a.n_ssplit, 64, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -441,5 +452,29 @@ int launch_attn_fwd_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
 int launch_attn_bwd_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 int launch_attn_bwd_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 int launch_attn_bwd_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+// the half path (sngnn_attn_forward_half / sngnn_attn_backward_half: h, out, gout and grad_h stored as S), one
+// translation unit per storage type and VEC (attn_f16_v*.hip, attn_bf16_v*.hip)
+template <typename S> struct LaunchAttnHalf {
+    template <int VEC, int G, int R> static int fwd(const AttnArgs &a, hipStream_t st)
+    {
+        return launch_attn_fwd<VEC, G, R, S>(a, st);
+    }
+    template <int VEC, int G, int R> static int bwd(const BwdArgs &a, hipStream_t st)
+    {
+        return launch_attn_bwd<VEC, G, R, S>(a, st);
+    }
+};
+int launch_attn_fwd_f16_v1(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_fwd_f16_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_fwd_f16_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_fwd_bf16_v1(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_fwd_bf16_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_fwd_bf16_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+int launch_attn_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_attn_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_attn_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_attn_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_attn_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+int launch_attn_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 
 }  // namespace sngnn

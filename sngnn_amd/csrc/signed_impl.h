@@ -39,6 +39,15 @@ struct SignedArgs {
     const int32_t *task_slot, *task_chunk, *split_task0;
     float *partial;              // [n_tasks][C]
     int nbA, nbB;
+    // Wh and out in their storage type S (the kernels' template parameter): float, or __half / __hip_bfloat16 for
+    // the half path (sngnn_signed_forward_half).  coef, c2, s and the task partials stay fp32.
+    template <typename S> __device__ __forceinline__ const S *rows() const { return reinterpret_cast<const S *>(h); }
+    template <typename S> __device__ __forceinline__ S *outs() const { return reinterpret_cast<S *>(out); }
+    template <typename S> __device__ __forceinline__ decltype(auto) out_at(size_t idx) const
+    {
+        if constexpr (std::is_same<S, float>::value) return (out[idx]);
+        else return HalfRef<S>{outs<S>() + idx};
+    }
 };
 
 constexpr int SIGNED_LDS = 3 * WAVE_T;    // words per wave: source ids | a_e | s_e (or t_e)
@@ -46,7 +55,7 @@ constexpr int SIGNED_LDS = 3 * WAVE_T;    // words per wave: source ids | a_e | 
 __device__ __forceinline__ float signed_kappa(float s, float cp, float cn) { return s > 0.f ? cp : (s < 0.f ? cn : 0.f); }
 
 // ------------------------------ forward ------------------------------------
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void signed_small(const SignedArgs &a, int blk, int *lds_wave, float cp, float cn)
 {
     using RowT = Row<VEC, G, R>;
@@ -65,15 +74,15 @@ __device__ __forceinline__ void signed_small(const SignedArgs &a, int blk, int *
         s_a[t] = a.coef[rs + t];
     }
     RowT hi, acc;
-    hi.load(a.h + (size_t)(a.row_off + i) * a.C, a.C, lg);
+    hi.load(a.rows<S>() + (size_t)(a.row_off + i) * a.C, a.C, lg);
     const float inv_i = inv_norm_of(group_sum<G>(hi.dot_partial(hi)));
     acc.zero();
     wave_lds_sync();
     for (int t0 = 0; t0 < deg; t0 += 2) {
         const bool two = t0 + 1 < deg;
         RowT x0, x1;
-        x0.load(a.h + (size_t)s_j[t0] * a.C, a.C, lg);
-        x1.load(a.h + (size_t)s_j[two ? t0 + 1 : t0] * a.C, a.C, lg);
+        x0.load(a.rows<S>() + (size_t)s_j[t0] * a.C, a.C, lg);
+        x1.load(a.rows<S>() + (size_t)s_j[two ? t0 + 1 : t0] * a.C, a.C, lg);
         const float e0 = edge_score<VEC, G, R>(hi, inv_i, x0);
         const float e1 = edge_score<VEC, G, R>(hi, inv_i, x1);
         fma_row<VEC, G, R>(acc, s_a[t0] * signed_kappa(e0, cp, cn) * e0, x0);
@@ -83,14 +92,14 @@ __device__ __forceinline__ void signed_small(const SignedArgs &a, int blk, int *
             if (lg == 0) s_e[t0 + 1] = e1;
         }
     }
-    acc.store(a.out + (size_t)i * a.C, a.C, lg);
+    acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     if (a.s) {
         wave_lds_sync();
         for (int t = lg; t < deg; t += G) a.s[rs + t] = s_e[t];
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void signed_wave(const SignedArgs &a, int blk, int *lds_wave, bool task, float cp, float cn)
 {
     using RowT = Row<VEC, G, R>;
@@ -118,7 +127,7 @@ __device__ __forceinline__ void signed_wave(const SignedArgs &a, int blk, int *l
         s_a[t] = a.coef[rs + e0 + t];
     }
     RowT hi, acc;
-    hi.load(a.h + (size_t)(a.row_off + i) * a.C, a.C, lg);
+    hi.load(a.rows<S>() + (size_t)(a.row_off + i) * a.C, a.C, lg);
     const float inv_i = inv_norm_of(group_sum<G>(hi.dot_partial(hi)));
     acc.zero();
     wave_lds_sync();
@@ -128,8 +137,8 @@ __device__ __forceinline__ void signed_wave(const SignedArgs &a, int blk, int *l
         const int qa = min(q0 + gid, n - 1), qb = min(q0 + NG + gid, n - 1);
         const bool la = q0 + gid < n, lb = q0 + NG + gid < n;
         RowT xa, xb;
-        xa.load(a.h + (size_t)s_j[qa] * a.C, a.C, lg);
-        xb.load(a.h + (size_t)s_j[qb] * a.C, a.C, lg);
+        xa.load(a.rows<S>() + (size_t)s_j[qa] * a.C, a.C, lg);
+        xb.load(a.rows<S>() + (size_t)s_j[qb] * a.C, a.C, lg);
         const float ea = edge_score<VEC, G, R>(hi, inv_i, xa);
         const float eb = edge_score<VEC, G, R>(hi, inv_i, xb);
         fma_row<VEC, G, R>(acc, la ? s_a[qa] * signed_kappa(ea, cp, cn) * ea : 0.f, xa);
@@ -138,7 +147,12 @@ __device__ __forceinline__ void signed_wave(const SignedArgs &a, int blk, int *l
         if (lg == 0 && lb) s_e[qb] = eb;
     }
     acc.reduce_across_groups();
-    if (gid == 0) acc.store(task ? a.partial + (size_t)tq * a.C : a.out + (size_t)i * a.C, a.C, lg);
+    if constexpr (std::is_same<S, float>::value) {
+        if (gid == 0) acc.store(task ? a.partial + (size_t)tq * a.C : a.out + (size_t)i * a.C, a.C, lg);
+    } else if (gid == 0) {                                // (a task's partial row stays fp32)
+        if (task) acc.store(a.partial + (size_t)tq * a.C, a.C, lg);
+        else acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
+    }
     if (a.s) {
         wave_lds_sync();
         for (int t = lane; t < n; t += 64) a.s[rs + e0 + t] = s_e[t];
@@ -146,20 +160,21 @@ __device__ __forceinline__ void signed_wave(const SignedArgs &a, int blk, int *l
     wave_lds_sync();
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_signed_fwd(const SignedArgs a)
 {
     __shared__ int lds[WAVES][SIGNED_LDS];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
     const float cp = a.c2[0], cn = a.c2[1];
-    if (b < a.nbA) signed_wave<VEC, G, R>(a, b, lw, true, cp, cn);
-    else if (b < a.nbA + a.nbB) signed_wave<VEC, G, R>(a, b - a.nbA, lw, false, cp, cn);
-    else signed_small<VEC, G, R>(a, b - a.nbA - a.nbB, lw, cp, cn);
+    if (b < a.nbA) signed_wave<VEC, G, R, S>(a, b, lw, true, cp, cn);
+    else if (b < a.nbA + a.nbB) signed_wave<VEC, G, R, S>(a, b - a.nbA, lw, false, cp, cn);
+    else signed_small<VEC, G, R, S>(a, b - a.nbA - a.nbB, lw, cp, cn);
 }
 
 // split rows: the tasks' partial rows added in task order (four chains, combined in fixed order)
-static __global__ __launch_bounds__(256) void k_signed_fin(const SignedArgs a)
+// (S: out is stored in the storage type - the fp32 total rounded once)
+template <typename S = float> __global__ __launch_bounds__(256) void k_signed_fin(const SignedArgs a)
 {
     __shared__ float s[4][64];
     const int p = blockIdx.x;
@@ -173,20 +188,20 @@ static __global__ __launch_bounds__(256) void k_signed_fin(const SignedArgs a)
             for (int t = t0 + q; t < t1; t += 4) v += a.partial[(size_t)t * a.C + c];
         s[q][cl] = v;
         __syncthreads();
-        if (q == 0 && c < a.C) a.out[(size_t)i * a.C + c] = (s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl]);
+        if (q == 0 && c < a.C) a.out_at<S>((size_t)i * a.C + c) = (s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl]);
         __syncthreads();
     }
 }
 
-template <int VEC, int G, int R> int launch_signed_fwd(const SignedArgs &a0, hipStream_t st)
+template <int VEC, int G, int R, typename S = float> int launch_signed_fwd(const SignedArgs &a0, hipStream_t st)
 {
     constexpr int RPW = 64 / G;
     SignedArgs a = a0;
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
     const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_signed_fwd<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_split > 0) k_signed_fin<<<a.n_split, 256, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_signed_fwd<VEC, G, R, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.n_split > 0) k_signed_fin<S><<<a.n_split, 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -211,7 +226,7 @@ __device__ __forceinline__ float signed_t_edge(const Row<VEC, G, R> &x, const Ro
     return t;
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void signed_t_small(const BwdArgs &a, const SignedBwdExtra &x, int blk, int *lds_wave,
                                                float cp, float cn)
 {
@@ -234,15 +249,15 @@ __device__ __forceinline__ void signed_t_small(const BwdArgs &a, const SignedBwd
         s_a[t] = x.coef[rs + t] * signed_kappa(se, cp, cn);
     }
     RowT gp, acc;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     acc.zero();
     wave_lds_sync();
     for (int t0 = 0; t0 < deg; t0 += 2) {
         const bool two = t0 + 1 < deg;
         const int t1 = two ? t0 + 1 : t0;
         RowT x0, x1;
-        x0.load(a.h + (size_t)s_j[t0] * a.C, a.C, lg);
-        x1.load(a.h + (size_t)s_j[t1] * a.C, a.C, lg);
+        x0.load(a.hrows<S>() + (size_t)s_j[t0] * a.C, a.C, lg);
+        x1.load(a.hrows<S>() + (size_t)s_j[t1] * a.C, a.C, lg);
         const float ta = signed_t_edge<VEC, G, R>(x0, gp, s_a[t0], acc);
         const float tb = signed_t_edge<VEC, G, R>(x1, gp, two ? s_a[t1] : 0.f, acc);
         if (lg == 0) s_t[t0] = ta;
@@ -256,7 +271,7 @@ __device__ __forceinline__ void signed_t_small(const BwdArgs &a, const SignedBwd
     }
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __device__ __forceinline__ void signed_t_wave(const BwdArgs &a, const SignedBwdExtra &x, int blk, int *lds_wave,
                                               bool task, float cp, float cn)
 {
@@ -289,15 +304,15 @@ __device__ __forceinline__ void signed_t_wave(const BwdArgs &a, const SignedBwdE
         s_a[t] = x.coef[rs + e0 + t] * signed_kappa(se, cp, cn);
     }
     RowT gp, acc;
-    gp.load(a.gout + (size_t)i * a.C, a.C, lg);
+    gp.load(a.grows<S>() + (size_t)i * a.C, a.C, lg);
     acc.zero();
     wave_lds_sync();
     for (int q0 = 0; q0 < n; q0 += 2 * NG) {
         const int qa = min(q0 + gid, n - 1), qb = min(q0 + NG + gid, n - 1);
         const bool la = q0 + gid < n, lb = q0 + NG + gid < n;
         RowT xa, xb;
-        xa.load(a.h + (size_t)s_j[qa] * a.C, a.C, lg);
-        xb.load(a.h + (size_t)s_j[qb] * a.C, a.C, lg);
+        xa.load(a.hrows<S>() + (size_t)s_j[qa] * a.C, a.C, lg);
+        xb.load(a.hrows<S>() + (size_t)s_j[qb] * a.C, a.C, lg);
         const float ta = signed_t_edge<VEC, G, R>(xa, gp, la ? s_a[qa] : 0.f, acc);
         const float tb = signed_t_edge<VEC, G, R>(xb, gp, lb ? s_a[qb] : 0.f, acc);
         if (lg == 0 && la) s_t[qa] = ta;
@@ -313,33 +328,33 @@ __device__ __forceinline__ void signed_t_wave(const BwdArgs &a, const SignedBwdE
     wave_lds_sync();
 }
 
-template <int VEC, int G, int R>
+template <int VEC, int G, int R, typename S = float>
 __global__ __launch_bounds__(BLOCK) void k_signed_bwd_t(const BwdArgs a, const SignedBwdExtra x)
 {
     __shared__ __align__(16) int lds[WAVES][4 * WAVE_T];
     const int b = blockIdx.x;
     int *lw = lds[threadIdx.x >> 6];
     const float cp = x.c2[0], cn = x.c2[1];
-    if (b < a.nbA) signed_t_wave<VEC, G, R>(a, x, b, lw, true, cp, cn);
-    else if (b < a.nbA + a.nbB) signed_t_wave<VEC, G, R>(a, x, b - a.nbA, lw, false, cp, cn);
-    else signed_t_small<VEC, G, R>(a, x, b - a.nbA - a.nbB, lw, cp, cn);
+    if (b < a.nbA) signed_t_wave<VEC, G, R, S>(a, x, b, lw, true, cp, cn);
+    else if (b < a.nbA + a.nbB) signed_t_wave<VEC, G, R, S>(a, x, b - a.nbA, lw, false, cp, cn);
+    else signed_t_small<VEC, G, R, S>(a, x, b - a.nbA - a.nbB, lw, cp, cn);
 }
 
-template <int VEC, int G, int R> int launch_signed_bwd(const BwdArgs &a0, const SignedBwdExtra &x, hipStream_t st)
+template <int VEC, int G, int R, typename S = float> int launch_signed_bwd(const BwdArgs &a0, const SignedBwdExtra &x, hipStream_t st)
 {
     constexpr int RPW = 64 / G;
     BwdArgs a = a0;
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
     int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_signed_bwd_t<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a, x);
+    if (a.nbA + a.nbB + nbC > 0) k_signed_bwd_t<VEC, G, R, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a, x);
     if (a.n_split > 0) k_bwd_t_fin<<<a.n_split, 256, 0, st>>>(a);      // dnT of the split rows: partT rows of C floats
     // pass S: the aggregation's kernels on the records (every edge carries one; no mean division)
     a.nbA = ceil_div(a.n_stasks, WAVES);
     a.nbB = ceil_div(a.n_smed_end - a.n_ssplit, WAVES);
     nbC = ceil_div(a.Ntot - a.n_smed_end, (int64_t)WAVES * RPW);
-    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, true><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R><<<a.n_ssplit, 64, 0, st>>>(a);
+    if (a.nbA + a.nbB + nbC > 0) k_bwd_s<VEC, G, R, true, false, S><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    if (a.n_ssplit > 0) k_bwd_s_fin<VEC, G, R, S><<<a.n_ssplit, 64, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -350,5 +365,29 @@ int launch_signed_fwd_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st)
 int launch_signed_bwd_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
 int launch_signed_bwd_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
 int launch_signed_bwd_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+// the half path (sngnn_signed_forward_half / sngnn_signed_backward_half: Wh, out, gout and grad_wh stored as S), one
+// translation unit per storage type and VEC (signed_f16_v*.hip, signed_bf16_v*.hip)
+template <typename S> struct LaunchSignedHalf {
+    template <int VEC, int G, int R> static int fwd(const SignedArgs &a, hipStream_t st)
+    {
+        return launch_signed_fwd<VEC, G, R, S>(a, st);
+    }
+    template <int VEC, int G, int R> static int bwd(const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st)
+    {
+        return launch_signed_bwd<VEC, G, R, S>(a, x, st);
+    }
+};
+int launch_signed_fwd_f16_v1(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_fwd_f16_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_fwd_f16_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_fwd_bf16_v1(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_fwd_bf16_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_fwd_bf16_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+int launch_signed_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+int launch_signed_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+int launch_signed_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+int launch_signed_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+int launch_signed_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+int launch_signed_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
 
 }  // namespace sngnn

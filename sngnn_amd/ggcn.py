@@ -123,6 +123,8 @@ class GGCNlayer_SP(nn.Module):
             if dv.numel() != val.numel():
                 raise ValueError("degree_precompute must have adj's entries (GGCN.precompute_degree_s)")
             coef = val * F.softplus(self.deg_coeff[0] * dv + self.deg_coeff[1])       # adj * sc (:1508-1510)
+        if h.dtype in ops.HALF_DTYPES:
+            return self._forward_half(h, adj, coef)
         wh = ops.linear(h, self.fcn)
         if not self.use_sign:
             # :1544-1549: a plain weighted sparse product (diagonal included), no cosine - the same gather-sum
@@ -134,4 +136,21 @@ class GGCNlayer_SP(nn.Module):
         c = F.softmax(self.coeff, dim=-1)
         scale = F.softplus(self.scale)
         prop = ops.signed_propagate(wh, coef[st.perm], c[:2], st.graph)       # c0 prop_pos + c1 prop_neg
+        return scale * (prop + c[2] * wh)
+
+    def _forward_half(self, h, adj, coef):
+        """The layer cast to float16 / bfloat16 on features of that type: ``fcn`` is torch's F.linear, the signed
+        propagation the library's half kernels (``sngnn_signed_forward_half``: the fp32 operator on Wh.float(), only
+        its output rounded to the type).  The per-entry coefficients and c_pos / c_neg go in as fp32 - autograd
+        carries their gradients back through the cast -, ``scale * (prop + c_2 Wh)`` runs in torch in the half
+        type.  use_sign=False has no half kernel: the fp32 weighted gather-sum on Wh.float(), cast back (as the
+        SNGNN++ adjacency branch does, conv.py)."""
+        wh = F.linear(h, self.fcn.weight, self.fcn.bias)
+        if not self.use_sign:
+            graph, perm, aux = self._adj(adj).full()
+            return ops.weighted_propagate(wh.float(), coef[perm].float(), graph, aux).to(wh.dtype)
+        st = self._adj(adj)
+        c = F.softmax(self.coeff, dim=-1)
+        scale = F.softplus(self.scale)
+        prop = ops.signed_propagate(wh, coef[st.perm].float(), c[:2].float(), st.graph)
         return scale * (prop + c[2] * wh)

@@ -16,8 +16,8 @@ from . import _lib
 from .graph import Graph
 
 
-# storage types of the half path (sngnn_agg_forward_half / sngnn_agg_backward_half): the fp32 operator on
-# h.float(), only the stored rows rounded once to the type
+# storage types of the half path (sngnn_agg_forward_half / sngnn_agg_backward_half, sngnn_attn_*_half,
+# sngnn_signed_*_half): the fp32 operator on h.float(), only the stored rows rounded once to the type
 HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
@@ -450,23 +450,42 @@ def aggregate(h: torch.Tensor, graph: Graph, top_k: Optional[int], thr: float,
 
 def attention_forward(graph: Graph, h: torch.Tensor, save_for_backward: bool = True):
     """``sngnn_attn_forward``: softmax-of-cosine attention (AGNNConv after ``lin``,
-    models.py:396-405).  Returns (out [N, C], alpha [E'] in CSR order or None)."""
-    h = _check_rows(h, graph.num_total_nodes, "h")
+    models.py:396-405).  Returns (out [N, C], alpha [E'] in CSR order or None).  A float16 / bfloat16
+    ``h`` takes the half path (``sngnn_attn_forward_half``): ``out`` in h's dtype - the fp32 operator on
+    h.float(), its rows rounded once -, ``alpha`` fp32 and bit-equal to that call's."""
+    h = _check_rows(h, graph.num_total_nodes, "h", half=True)
     c = h.size(1)
-    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=h.device)
+    out = torch.empty((graph.num_nodes, c), dtype=h.dtype, device=h.device)
     alpha = (torch.empty(graph.num_edges, dtype=torch.float32, device=h.device)
              if save_for_backward else None)
-    _lib.call("sngnn_attn_forward", h.device, graph.handle, h, c, out, alpha, graph.workspace(c))
+    if h.dtype in HALF_DTYPES:
+        _lib.call("sngnn_attn_forward_half", h.device, graph.handle, h, HALF_DTYPES[h.dtype], c, out, alpha,
+                  graph.workspace(c))
+    else:
+        _lib.call("sngnn_attn_forward", h.device, graph.handle, h, c, out, alpha, graph.workspace(c))
     return out, alpha
+
+
+def _check_grad_dtype(grad_out: torch.Tensor, rows: torch.Tensor, what: str) -> None:
+    """``grad_out`` of a half call has the rows' dtype; of an fp32 call, float32."""
+    if grad_out.dtype != rows.dtype:
+        raise ValueError(f"grad_out must have {what}'s dtype {rows.dtype}, got {grad_out.dtype}")
 
 
 def attention_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
                        alpha: torch.Tensor) -> torch.Tensor:
-    h = _check_rows(h, graph.num_total_nodes, "h")
-    grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out")
+    """``sngnn_attn_backward``; a float16 / bfloat16 ``h`` (and ``grad_out`` of the same dtype) takes
+    ``sngnn_attn_backward_half``: ``grad_h`` in that dtype, the fp32 backward on the widened rows rounded once."""
+    h = _check_rows(h, graph.num_total_nodes, "h", half=True)
+    grad_out = _check_rows(grad_out, graph.num_nodes, "grad_out", half=True)
+    _check_grad_dtype(grad_out, h, "h")
     c = h.size(1)
     grad_h = torch.empty_like(h)
-    _lib.call("sngnn_attn_backward", h.device, graph.handle, h, c, grad_out, alpha, grad_h, graph.workspace(c))
+    if h.dtype in HALF_DTYPES:
+        _lib.call("sngnn_attn_backward_half", h.device, graph.handle, h, HALF_DTYPES[h.dtype], c, grad_out, alpha,
+                  grad_h, graph.workspace(c))
+    else:
+        _lib.call("sngnn_attn_backward", h.device, graph.handle, h, c, grad_out, alpha, grad_h, graph.workspace(c))
     return grad_h
 
 
@@ -495,31 +514,44 @@ def attention(h: torch.Tensor, graph: Graph) -> torch.Tensor:
 
 def signed_forward(graph: Graph, wh: torch.Tensor, coef: torch.Tensor, c2: torch.Tensor):
     """``sngnn_signed_forward``: (out [N, C], s [E'] the cosines in the graph's CSR order).  ``coef`` [E'] = a_e
-    in CSR order, ``c2`` [2] device scalars (c_pos, c_neg)."""
-    wh = _check_rows(wh, graph.num_total_nodes, "wh")
+    in CSR order, ``c2`` [2] device scalars (c_pos, c_neg).  A float16 / bfloat16 ``wh`` takes the half path
+    (``sngnn_signed_forward_half``): ``out`` in wh's dtype - the fp32 operator on wh.float(), its rows rounded
+    once -; ``coef``, ``c2`` and ``s`` stay fp32, ``s`` bit-equal to that call's."""
+    wh = _check_rows(wh, graph.num_total_nodes, "wh", half=True)
     c = wh.size(1)
     if coef.dtype != torch.float32 or coef.numel() != graph.num_edges or not coef.is_cuda:
         raise ValueError("coef must be a float32 GPU tensor with one entry per edge of the graph")
     if c2.dtype != torch.float32 or c2.numel() != 2 or not c2.is_cuda:
         raise ValueError("c2 must be a float32 GPU tensor of 2 elements")
     coef, c2 = coef.contiguous(), c2.contiguous()
-    out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=wh.device)
+    out = torch.empty((graph.num_nodes, c), dtype=wh.dtype, device=wh.device)
     s = torch.empty(graph.num_edges, dtype=torch.float32, device=wh.device)
-    _lib.call("sngnn_signed_forward", wh.device, graph.handle, wh, c, coef, c2, out, s, graph.workspace(c))
+    if wh.dtype in HALF_DTYPES:
+        _lib.call("sngnn_signed_forward_half", wh.device, graph.handle, wh, HALF_DTYPES[wh.dtype], c, coef, c2, out, s,
+                  graph.workspace(c))
+    else:
+        _lib.call("sngnn_signed_forward", wh.device, graph.handle, wh, c, coef, c2, out, s, graph.workspace(c))
     return out, s
 
 
 def signed_backward(graph: Graph, wh: torch.Tensor, grad_out: torch.Tensor, coef: torch.Tensor, s: torch.Tensor,
                     c2: torch.Tensor):
     """``sngnn_signed_backward``: (grad_wh [N_total, C], u [E'] = s_e <G_i, Wh_j> in CSR order) from the forward's
-    saved cosines ``s``."""
-    wh = _check_rows(wh, graph.num_total_nodes, "wh")
-    g = _check_rows(grad_out.contiguous(), graph.num_nodes, "grad_out")
+    saved cosines ``s``.  A float16 / bfloat16 ``wh`` (and ``grad_out`` of the same dtype) takes
+    ``sngnn_signed_backward_half``: ``grad_wh`` in that dtype, ``u`` fp32 and bit-equal to the fp32 call's."""
+    wh = _check_rows(wh, graph.num_total_nodes, "wh", half=True)
+    g = _check_rows(grad_out.contiguous(), graph.num_nodes, "grad_out", half=True)
+    _check_grad_dtype(g, wh, "wh")
     c = wh.size(1)
     coef, c2, s = coef.contiguous(), c2.contiguous(), s.contiguous()
     grad_wh = torch.empty_like(wh)
     u = torch.empty_like(s)
-    _lib.call("sngnn_signed_backward", wh.device, graph.handle, wh, c, g, coef, s, c2, grad_wh, u, graph.workspace(c))
+    if wh.dtype in HALF_DTYPES:
+        _lib.call("sngnn_signed_backward_half", wh.device, graph.handle, wh, HALF_DTYPES[wh.dtype], c, g, coef, s, c2,
+                  grad_wh, u, graph.workspace(c))
+    else:
+        _lib.call("sngnn_signed_backward", wh.device, graph.handle, wh, c, g, coef, s, c2, grad_wh, u,
+                  graph.workspace(c))
     return grad_wh, u
 
 
@@ -532,7 +564,7 @@ class _SignedPropagate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, wh, coef, c2, graph):
-        wh = _check_rows(wh, graph.num_total_nodes, "wh")
+        wh = _check_rows(wh, graph.num_total_nodes, "wh", half=True)
         coef, c2 = coef.contiguous(), c2.contiguous()
         out, s = signed_forward(graph, wh, coef, c2)
         ctx.graph = graph

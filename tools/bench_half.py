@@ -9,11 +9,14 @@ fp16, and bf16 / fp16 with the rows padded by zero channels to the width their 1
             decisions in doubt and re-scored exactly) - the on-the-fly form's worst case
   products  config 5's graph (products size), one SNGNN_Plus_Plus layer's aggregation, top_k 16, thr 0, C 48;
             plus the adjacency branch as the half layer runs it (ops.adj_linear on an fp32 copy of w)
+  attention config 4's graph (arxiv size), C 40: the cosine attention (AGNNConv's operator) and the signed cosine
+            attention (GGCNlayer_SP's), forward and backward, fp32 / bf16 / fp16 on the same two graph objects in
+            this process; the forms alternate over --rounds rounds (median and spread per form, half / fp32 ratio)
 Warm-up as bench.py: an untimed preheat of the same step (--preheat-ms), W warm-up steps, K timed steps.
 Per form: algorithmic bytes (bench.algorithmic_bytes / backward_bytes with 2-byte rows for the half forms)
 and their fraction of 8 TB/s.  One JSON line per (case, form, pass); --json FILE writes them all.
 
-    python tools/bench_half.py [--cases arxiv,parallel,products] [--steps 50] [--warmup 10]
+    python tools/bench_half.py [--cases arxiv,parallel,products,attention] [--steps 50] [--warmup 10]
 Kernel figures: run it under ``rocprofv3 --kernel-trace --stats``; counters (FETCH_SIZE) in a run of their own.
 """
 import argparse
@@ -28,7 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from sngnn_amd import _lib, conv, ops  # noqa: E402
-from sngnn_amd.graph import Graph  # noqa: E402
+from sngnn_amd.graph import LOOPS_REPLACE, Graph  # noqa: E402
 
 PEAK = 8.0e12
 
@@ -99,9 +102,49 @@ def run_case(name, g, h32, k, thr, args, records, extra=None):
         extra(records)
 
 
+def run_attention(n, ei, h32, args, records):
+    """The two attention modes, half against fp32: same graph objects, same process; per pass the forms are timed
+    in turn, --rounds times over (a drift of the machine hits every form alike), median per form."""
+    c = h32.size(1)
+    dev = h32.device
+    g_attn = Graph(ei, n, True, LOOPS_REPLACE)                # as AGNNConv builds it
+    g_sign = Graph(ei, n, False, True)                        # as GGCNlayer_SP builds it (adj_remove_diag)
+    gen = torch.Generator(device=dev).manual_seed(9)
+    go32 = torch.randn(n, c, device=dev, generator=gen)
+    coef = torch.randn(g_sign.num_edges, device=dev, generator=gen)
+    c2 = torch.tensor([0.7, 0.2], device=dev)
+    forms = [("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp16", torch.float16)]
+    steps = {}
+    for form, D in forms:
+        h, go = h32.to(D).contiguous(), go32.to(D).contiguous()
+        _, alpha = ops.attention_forward(g_attn, h, True)
+        _, s = ops.signed_forward(g_sign, h, coef, c2)
+        steps[form] = {
+            "attn_fwd": (lambda h=h: ops.attention_forward(g_attn, h, True)),
+            "attn_bwd": (lambda h=h, go=go, alpha=alpha: ops.attention_backward(g_attn, h, go, alpha)),
+            "signed_fwd": (lambda h=h: ops.signed_forward(g_sign, h, coef, c2)),
+            "signed_bwd": (lambda h=h, go=go, s=s: ops.signed_backward(g_sign, h, go, coef, s, c2)),
+        }
+    for pas in ("attn_fwd", "attn_bwd", "signed_fwd", "signed_bwd"):
+        ms = {form: [] for form, _ in forms}
+        for _ in range(args.rounds):
+            for form, _ in forms:
+                ms[form].append(timed(steps[form][pas], args.steps, args.warmup, args.preheat_ms))
+        med = {form: float(np.median(v)) for form, v in ms.items()}
+        e_prime = (g_attn if pas.startswith("attn") else g_sign).num_edges
+        for form, D in forms:
+            rec = dict(case="attention", op=pas, form=form, C=c, n=n, e_prime=e_prime,
+                       ms_median=round(med[form], 4), ms_min=round(min(ms[form]), 4), ms_max=round(max(ms[form]), 4),
+                       ratio_to_fp32=round(med[form] / med["fp32"], 4), rounds=args.rounds, steps=args.steps,
+                       warmup=args.warmup)
+            print(json.dumps(rec), flush=True)
+            records.append(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cases", default="arxiv,parallel,products")
+    ap.add_argument("--cases", default="arxiv,parallel,products,attention")
+    ap.add_argument("--rounds", type=int, default=3, help="attention case: alternating rounds per form")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--preheat-ms", type=float, default=60.0)
@@ -110,8 +153,10 @@ def main():
     dev = torch.device("cuda:0")
     records = []
     cases = args.cases.split(",")
-    if "arxiv" in cases or "parallel" in cases:
+    if "arxiv" in cases or "parallel" in cases or "attention" in cases:
         n, c, ei, x, h, lin = bench.make_rank_inputs("arxiv", 0, 1, 1234, dev)
+        if "attention" in cases:
+            run_attention(n, ei, h, args, records)
         g = Graph(ei, n, True, True)
         if "arxiv" in cases:
             for thr in (0.0, 0.9):
