@@ -476,6 +476,37 @@ int sngnn_blend_backward_epilogue(const float *grad_out, const float *out0, cons
                                   void *stream);
 
 /*
+ * Replaces: GGCN's layer transition - the last line of GGCNlayer_SP, `scale*(coeff[0]*prop_pos+coeff[1]*prop_neg+
+ * coeff[2]*Wh)` (models.py:1544; prop = coeff[0]*prop_pos + coeff[1]*prop_neg is sngnn_signed_forward's output), and
+ * between two layers the model's `act_fn`, `layer_inner + layer_previous` / `coeff*layer_inner + layer_previous`
+ * (models.py:1720, 1726-1736) - and their autograd: about fifteen elementwise passes over [N, C] per layer as one pass
+ * each way over the n = N * C elements.  cs dev f32 [2] = (c2, scale), coeff a host float.
+ *   flags bit 0 (ACT) clear - combine, the last layer's output (prev, coeff unused):
+ *     out = y = scale * (prop + c2 * wh)       every product and sum rounded separately, in this order: the torch
+ *                                              expression scale * (prop + c[2] * Wh) bit for bit
+ *   ACT set - transition:  out = coeff * elu(y) + p,  elu(v) = v > 0 ? v : expm1f(v),
+ *     p = prev, or elu(prev) with bit 1 (PREV_ELU; needs ACT): the first transition, prev = fcn(x), coeff = 1
+ *   wh == NULL && cs == NULL: y = prop (use_sign=False, models.py:1546-1552); one of them NULL alone is an error.
+ * Backward (nothing saved by the forward: prop and wh are read again), g = grad_out:
+ *   gy = coeff * g * (y > 0 ? 1 : expf(y))  (g itself without ACT),  grad_prop = scale * gy,  grad_wh = c2 * grad_prop,
+ *   grad_cs [2] = (scale * sum gy * wh,  sum gy * (prop + c2 * wh))  - per-block partials, then one block adds them
+ *   in double in a fixed order (no atomics);  PREV_ELU: grad_prev = g * (prev > 0 ? 1 : expf(prev)); otherwise the
+ *   gradient of prev is grad_out itself and grad_prev (and prev) are not touched.  Without wh / cs, grad_wh, grad_cs
+ *   and workspace are not touched.  workspace: sngnn_ggcn_transition_workspace_bytes().
+ * n == 0 is SNGNN_OK whatever the tensors' pointers are (the backward then writes grad_cs = 0 if cs is given).
+ * NULL where required, wh without cs, PREV_ELU without ACT or a negative n return SNGNN_EINVAL without a
+ * launch.  float4 accesses when every pointer is 16-byte aligned, scalar ones otherwise.
+ */
+#define SNGNN_GGCN_ACT       1
+#define SNGNN_GGCN_PREV_ELU  2
+int64_t sngnn_ggcn_transition_workspace_bytes(void);
+int sngnn_ggcn_transition_forward(const float *prop, const float *wh, const float *cs, const float *prev,
+                                  float coeff, int flags, int64_t n, float *out, void *stream);
+int sngnn_ggcn_transition_backward(const float *grad_out, const float *prop, const float *wh, const float *cs,
+                                   const float *prev, float coeff, int flags, int64_t n, float *grad_prop,
+                                   float *grad_wh, float *grad_prev, float *grad_cs, void *workspace, void *stream);
+
+/*
  * The same two gather-sums on any graph, node-range partitions included (multi-GPU
  * SNGNN++; new - the reference is single-device).  A rank builds the partition of the
  * FLIPPED edge list (row 0 and row 1 of edge_index swapped), whose owned "targets" are

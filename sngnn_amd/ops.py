@@ -973,6 +973,92 @@ def blend(out0: torch.Tensor, out1: torch.Tensor, beta: torch.Tensor,
     return beta * out0 + (1 - beta) * out1
 
 
+GGCN_ACT, GGCN_PREV_ELU = 1, 2          # SNGNN_GGCN_*: the flags of sngnn_ggcn_transition_forward / _backward
+
+
+def _check_flat(t: torch.Tensor, like: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise ValueError(f"{what} must be a float32 tensor (the fused GGCN transition is fp32 only)")
+    if not t.is_cuda:
+        raise ValueError(f"{what} must live on the GPU (there is no CPU path)")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous, got shape {tuple(t.shape)} with strides {t.stride()}")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{what} must have prop's shape {tuple(like.shape)} and device, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+class _GGCNTransition(torch.autograd.Function):
+    """GGCN's layer transition in one pass each way (``sngnn_ggcn_transition_forward`` / ``_backward``):
+    ``y = cs[1] * (prop + cs[0] * wh)`` (models.py:1544; ``y = prop`` without ``wh`` / ``cs``: use_sign=False) and,
+    with GGCN_ACT, ``coeff * elu(y) + prev`` (models.py:1726-1736; GGCN_PREV_ELU: ``+ elu(prev)``, :1720).  Nothing but
+    the inputs is saved: the backward forms ``y`` again."""
+
+    @staticmethod
+    def forward(ctx, prop, wh, cs, prev, coeff, flags):
+        out = torch.empty_like(prop)
+        if wh is not None:          # the backward's scratch exists before a capture whose first backward is captured
+            _workspace("ggcn_transition", _lib.load().sngnn_ggcn_transition_workspace_bytes(), prop.device)
+        _lib.call("sngnn_ggcn_transition_forward", prop.device, prop, wh, cs, prev, float(coeff), int(flags), prop.numel(),
+                  out)
+        ctx.coeff, ctx.flags = float(coeff), int(flags)
+        ctx.save_for_backward(prop, wh, cs, prev if flags & GGCN_PREV_ELU else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        prop, wh, cs, prev = ctx.saved_tensors
+        g = g.contiguous()
+        grad_prop = torch.empty_like(prop)
+        grad_wh = grad_cs = ws = grad_prev = None
+        if wh is not None:
+            grad_wh, grad_cs = torch.empty_like(wh), torch.empty_like(cs)
+            ws = _workspace("ggcn_transition", _lib.load().sngnn_ggcn_transition_workspace_bytes(), g.device)
+        if ctx.flags & GGCN_PREV_ELU:
+            grad_prev = torch.empty_like(prev)
+        _lib.call("sngnn_ggcn_transition_backward", g.device, g, prop, wh, cs, prev, ctx.coeff, ctx.flags, prop.numel(),
+                  grad_prop, grad_wh, grad_prev, grad_cs, ws)
+        if ctx.flags == GGCN_ACT:
+            grad_prev = g                     # out = ... + prev
+        return grad_prop, grad_wh, grad_cs, grad_prev, None, None
+
+
+def _check_transition(prop, wh, cs, prev):
+    if (wh is None) != (cs is None):
+        raise ValueError("wh and cs go together (both None: y = prop, the use_sign=False layer)")
+    prop = _check_flat(prop, None, "prop")
+    if wh is not None:
+        _check_flat(wh, prop, "wh")
+        if not torch.is_tensor(cs) or cs.dtype != torch.float32 or not cs.is_cuda or cs.numel() != 2 or cs.device != prop.device:
+            raise ValueError("cs must be a float32 GPU tensor of 2 elements (c2, scale) on prop's device")
+        cs = cs.contiguous()
+    if prev is not None:
+        _check_flat(prev, prop, "prev")
+    return prop, wh, cs, prev
+
+
+def ggcn_combine(prop: torch.Tensor, wh: torch.Tensor, cs: torch.Tensor) -> torch.Tensor:
+    """The last line of GGCNlayer_SP (models.py:1544), ``cs[1] * (prop + cs[0] * wh)`` with ``cs`` = (c2, scale) a
+    device tensor of 2 elements: one pass forward (the torch expression bit for bit), one backward with both scalar
+    gradients as fixed-order sums.  Contiguous fp32 GPU tensors of one shape; everything else raises."""
+    if wh is None or cs is None:
+        raise ValueError("ggcn_combine needs wh and cs (without them the layer's output is prop itself)")
+    prop, wh, cs, _ = _check_transition(prop, wh, cs, None)
+    return _GGCNTransition.apply(prop, wh, cs, None, 1.0, 0)
+
+
+def ggcn_transition(prop: torch.Tensor, wh: Optional[torch.Tensor], cs: Optional[torch.Tensor], prev: torch.Tensor,
+                    coeff: float, prev_elu: bool = False) -> torch.Tensor:
+    """GGCN between two layers (models.py:1544 + 1720-1736) in one pass each way: ``coeff * elu(y) + p`` with
+    ``y = cs[1] * (prop + cs[0] * wh)`` (``y = prop`` when ``wh`` and ``cs`` are None: use_sign=False) and ``p = prev``,
+    or ``elu(prev)`` with ``prev_elu`` (the first transition, where prev = fcn(x) and coeff = 1).  ``coeff`` is a host
+    float.  Contiguous fp32 GPU tensors of one shape; everything else raises."""
+    if prev is None:
+        raise ValueError("ggcn_transition needs prev (the last layer's output is ggcn_combine)")
+    prop, wh, cs, prev = _check_transition(prop, wh, cs, prev)
+    return _GGCNTransition.apply(prop, wh, cs, prev, float(coeff), GGCN_ACT | (GGCN_PREV_ELU if prev_elu else 0))
+
+
 def _head_nll(logits, y, row_mask_u8, n_masked, out, want_grad: bool):
     """``sngnn_head_nll``: (fp32 [2] = (mean NLL, n_correct) - ``out`` if given -, d loss / d logits or None)."""
     z = logits.contiguous()
