@@ -507,6 +507,37 @@ int sngnn_ggcn_transition_backward(const float *grad_out, const float *prop, con
                                    float *grad_wh, float *grad_prev, float *grad_cs, void *workspace, void *stream);
 
 /*
+ * Replaces: what the model wrappers run between two conv layers in TRAINING with bn=True (models.py:204-209, 79-84,
+ * 296-301, 368-373): the conv's bias add (:135-136, 240-241, 327-328), `F.relu(x, inplace=True)`, `self.bns[i](x)` on the
+ * batch's statistics and `self.dropout(x)` - about nine passes over [N, C] forward and eleven backward as three
+ * launches each way (partials per workgroup, one small reducer, apply).  fp32, x / out / grad_* dense [N, C]:
+ *   z = x + bias (bias NULL: z = x),  r = max(z, 0),  mean_c = sum_i r / N,  var_c = sum_i (r - mean)^2 / N (biased),
+ *   invstd = 1 / sqrt(var + eps),  xhat = (r - mean) * invstd,  out = (xhat * gamma + beta) * keep * keep_scale
+ * keep: the caller's u8 [N, C] mask, or drawn in the kernel from (seed, i * C + c) as sngnn_epilogue_t.seed documents
+ * (seed: dev uint64 [1], used when p > 0), or neither: no dropout.  The relu is idempotent, so rows a producer already
+ * stored as relu(conv + bias) go in with bias NULL.  The forward also writes save_mean / save_invstd [C] and, when
+ * given, running_mean <- (1 - momentum) running_mean + momentum mean, running_var <- ... + momentum var N / (N - 1).
+ * Nothing of size [N, C] is saved: the backward recomputes r, xhat and the mask from x.  With gz = grad_out * keep *
+ * keep_scale:  grad_beta = sum_i gz,  grad_gamma = sum_i gz xhat,
+ *   grad_x = invstd * (gamma gz - gamma grad_beta / N - xhat gamma grad_gamma / N) * [z > 0],
+ * and grad_bias (optional; needs bias) = the column sums of grad_x.  Every sum is accumulated in double; the statistics
+ * as (count, mean, M2) partials combined by Chan's formula, never as sum r^2.  No atomics: the same bits every run.
+ * Only enqueues.  workspace: sngnn_bn_train_workspace_bytes(C) (0 for a C out of range).
+ * NULL where required, N < 2, C < 1 or > SNGNN_MAX_CHANNELS, p outside [0, 1), keep together with seed, grad_bias
+ * without bias, or one of running_mean / running_var alone return SNGNN_EINVAL without a launch.  float4 accesses
+ * where C % 4 == 0 and every [N, C] base is 16-byte aligned, scalar ones otherwise.
+ */
+int64_t sngnn_bn_train_workspace_bytes(int C);
+int sngnn_bn_train_forward(const float *x, const float *bias, int64_t N, int C, const float *gamma, const float *beta,
+                           double eps, double momentum, float *running_mean, float *running_var,
+                           const unsigned char *keep, float keep_scale, const void *seed, float p, float *out,
+                           float *save_mean, float *save_invstd, void *workspace, void *stream);
+int sngnn_bn_train_backward(const float *grad_out, const float *x, const float *bias, int64_t N, int C,
+                            const float *gamma, const float *save_mean, const float *save_invstd,
+                            const unsigned char *keep, float keep_scale, const void *seed, float p, float *grad_x,
+                            float *grad_gamma, float *grad_beta, float *grad_bias, void *workspace, void *stream);
+
+/*
  * The same two gather-sums on any graph, node-range partitions included (multi-GPU
  * SNGNN++; new - the reference is single-device).  A rank builds the partition of the
  * FLIPPED edge list (row 0 and row 1 of edge_index swapped), whose owned "targets" are

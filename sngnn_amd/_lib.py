@@ -84,6 +84,9 @@ SIGNATURES = {
     "sngnn_ggcn_transition_forward": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp]),
     "sngnn_ggcn_transition_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                               _vp]),
+    "sngnn_bn_train_workspace_bytes": (_i64, [_i32]),
+    "sngnn_bn_train_forward": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _f32, _vp, _f32] + [_vp] * 5),
+    "sngnn_bn_train_backward": (_i32, [_vp, _vp, _vp, _i64, _i32] + [_vp] * 4 + [_f32, _vp, _f32] + [_vp] * 6),
     "sngnn_knn_workspace_bytes": (_i64, [_i64, _i32]),
     "sngnn_knn_graph": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),

@@ -311,7 +311,10 @@ class SNConv(nn.Module):
             return ops.aggregate(h, graph, None, 0.0, None, epilogue, self.bias)
         out = _true_width(_aggregate(h, graph, shard, None, 0.0, table), c)
         if self.bias is not None:
-            out = out + self.bias
+            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
+                epilogue.bias = self.bias
+            else:
+                out = out + self.bias
         return out
 
 
@@ -399,7 +402,10 @@ class SNConv_plus(nn.Module):
             return ops.aggregate(h, graph, int(self.top_k), float(self.thr), unit, epilogue, self.bias)
         out = _true_width(_aggregate(h, graph, shard, int(self.top_k), float(self.thr), table, unit), c)
         if self.bias is not None:
-            out = out + self.bias
+            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
+                epilogue.bias = self.bias
+            else:
+                out = out + self.bias
         return out
 
 
@@ -615,5 +621,8 @@ class SNConv_plus_plus(nn.Module):
             return ops.blend(out_0, out_1, self.beta, epilogue)
         out = ops.blend(out_0, out_1, self.beta)
         if self.bias is not None:
-            out = out + self.bias
+            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
+                epilogue.bias = self.bias
+            else:
+                out = out + self.bias
         return out

@@ -18,6 +18,9 @@ from .conv import AGNNConv, SNConv, SNConv_plus, SNConv_plus_plus
 # A/B switch of the fused hidden-layer epilogue (_Stack.forward_logits; tests flip it, SNGNN_FUSE_HIDDEN=0
 # starts a process with it off)
 FUSE_HIDDEN = os.environ.get("SNGNN_FUSE_HIDDEN", "1") != "0"
+# A/B switch of the fused training-mode batch norm between two conv layers (ops.batch_norm_act; SNGNN_FUSE_BN=0 or
+# SNGNN_FUSE_HIDDEN=0 start a process with it off: the plain op sequence relu_ -> BatchNorm1d -> dropout)
+FUSE_BN = os.environ.get("SNGNN_FUSE_BN", "1") != "0"
 
 
 class _Stack(nn.Module):
@@ -56,10 +59,14 @@ class _Stack(nn.Module):
         # EVALUATION with batch norm (models.py:207-208): the running statistics are constants, so the norm is a
         # per-channel scale and shift - folded into the NEXT conv's ``lin`` (conv.LinFold) - and the conv's bias
         # + relu in front of it go into the aggregation's store epilogue: no elementwise pass is left between two
-        # conv layers.  (Training-mode batch norm needs the batch's statistics: the op sequence below.)
+        # conv layers.
         if (FUSE_HIDDEN and self.bn and not self.training and sn_dist.current_partition() is None and x.is_cuda
                 and x.dtype == torch.float32 and isinstance(self.lins[0], (SNConv, SNConv_plus))):
             return self._forward_logits_bn_eval(x, edge_index, head)
+        # TRAINING with batch norm: bias + relu + the norm on the batch's statistics + dropout between two conv
+        # layers as ops.batch_norm_act (three launches each way) instead of torch's op sequence below
+        if self._bn_train_fusable(x):
+            return self._forward_logits_bn_train(x, edge_index, head if takes_head else None)
         act = None
         seeds = self._dropout_seeds(x.device) if (fusable and len(self.lins) > 1 and self.training
                                                    and self.dropout.p > 0.0) else None
@@ -98,6 +105,45 @@ class _Stack(nn.Module):
         takes_head = head is not None and isinstance(self.lins[-1], (SNConv, SNConv_plus))
         return self.lins[-1](x, edge_index, None, None, head if takes_head else None, fold)
 
+    def _bn_train_fusable(self, x) -> bool:
+        """Whether a training forward's hidden transitions run as ``ops.batch_norm_act``: one GPU, fp32 features and
+        parameters, at least two rows (torch refuses fewer: its path keeps the error), plain affine BatchNorm1d
+        layers that track running statistics with a numeric momentum, at most SNGNN_MAX_CHANNELS wide."""
+        if not (FUSE_HIDDEN and FUSE_BN and self.bn and self.training and len(self.lins) > 1
+                and sn_dist.current_partition() is None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+                and x.size(0) >= 2 and self.lins[0].lin.weight.dtype == torch.float32):
+            return False
+        for bn in self.bns:
+            if not (type(bn) is nn.BatchNorm1d and bn.training and bn.affine and bn.track_running_stats
+                    and bn.running_mean is not None and isinstance(bn.momentum, (int, float))
+                    and bn.weight.dtype == torch.float32 and bn.weight.device == x.device
+                    and bn.num_features <= ops._lib.MAX_CHANNELS):
+                return False
+        return True
+
+    def _forward_logits_bn_train(self, x, edge_index, head):
+        p = float(self.dropout.p) if self.dropout.training else 0.0
+        seeds = self._dropout_seeds(x.device) if p > 0.0 else None
+        for i, lin in enumerate(self.lins[:-1]):
+            seed = None if seeds is None else seeds[i:i + 1]
+            if isinstance(lin, AGNNConv):                                # (no conv bias, no store epilogue)
+                x = ops.batch_norm_act(lin(x, edge_index), self.bns[i], None, p, None, seed)
+                continue
+            # conv bias + relu in the aggregation's stores where the layer takes them (as the evaluation path
+            # does): the activated rows go in with bias=None, and the producer's backward receives its gradient
+            # with relu' applied already (``premasked``).  A layer that declines (SNConv_plus_plus, a padded width)
+            # hands over its bias instead of adding it (``defer_bias``): the kernels add it.
+            epi = ops.HiddenEpilogue(True, 0.0, False)
+            epi.defer_bias = True
+            y = lin(x, edge_index, epi)
+            if epi.applied:
+                x = ops.batch_norm_act(y, self.bns[i], None, p, None, seed, epi)
+            else:
+                x = ops.batch_norm_act(y, self.bns[i], epi.bias, p, None, seed)
+        if head is not None:
+            return self.lins[-1](x, edge_index, None, None, head)
+        return self.lins[-1](x, edge_index)
+
     def forward(self, data):
         return F.log_softmax(self.forward_logits(data), dim=1)
 
@@ -128,6 +174,10 @@ class _Stack(nn.Module):
             s = getattr(self, "_drop_seed", None)
             if s is None or s.device != device or s.numel() != len(self.lins) - 1:
                 self._dropout_seeds(device)
+        if self.bn and len(self.lins) > 1 and device.type == "cuda" and FUSE_HIDDEN and FUSE_BN:
+            for bn in self.bns:          # the fused batch norm's scratch (ops.batch_norm_act)
+                if bn.num_features <= ops._lib.MAX_CHANNELS:
+                    ops.bn_train_workspace(bn.num_features, device)
 
     def _build(self, conv, in_channels, hidden_channels, out_channels, num_layers):
         self.lins = nn.ModuleList()

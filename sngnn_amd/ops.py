@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from .batchnorm import _BatchNormAct, batch_norm_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
 from .graph import Graph
 
 
