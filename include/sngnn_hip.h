@@ -566,6 +566,64 @@ int sngnn_weighted_scatter_sum_rows(const sngnn_graph_t *g, const float *vals, c
 int sngnn_pair_dot_rows(const float *a_rows, const int32_t *idx_a, const float *b_rows, const int32_t *idx_b,
                         int64_t n_pairs, int C, float *out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Polynomial propagation with the GCN-normalised adjacency (GPRGNN, APPNP): csrc/prop.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * A^ = D^-1/2 (A + I) D^-1/2 of PyG's gcn_norm(edge_index, None, N, add_self_loops=True): original self loops
+ * dropped, one loop per node appended, duplicates counted - the graph built with add_loops = 1, remove_loops =
+ * SNGNN_LOOPS_REPLACE, which every entry below requires (and an unpartitioned one: SNGNN_EINVAL otherwise) -,
+ * deg_i = in-degree with the loop (>= 1), dinv = deg^-1/2, (A^ x)_i = sum_{e -> i} dinv_src dinv_i x_src, and
+ * A^T the same sum over the out-edges (the CSC side; edge_index need not be symmetric).
+ *
+ * No weight is read per edge: the kernels carry the SCALED iterate u = dinv . x, so that (A^ x)_i = dinv_i S_i
+ * with S_i = sum_{e -> i} u_src an unweighted gather-sum on the row classes of the other gather kernels (lane
+ * group, wave, 128-edge tasks + finalize; fixed order, no atomics).  One hop is one launch sequence (main, +
+ * finalize when the side has split rows) whose store epilogue is
+ *     z_i = a x0_i + b (dinv_i S_i),   [acc_i += c z_i,]   [dot += <z_i, xd_i>,]   store dinv_i z_i | z_i (last hop)
+ * with a, b, c read from device memory; every product and sum rounded separately.  Hops are separate launches.
+ *
+ * sngnn_prop_dinv replaces gcn_norm's degree pass (deg = scatter_add of ones, deg.pow(-0.5)): dinv dev f32 [N]
+ * from the graph's own rowptr, once per graph.
+ */
+int sngnn_prop_dinv(const sngnn_graph_t *g, float *dinv, void *stream);
+/* bytes of device workspace of the three entries below at C channels and K hops: two scaled iterates [N, C], the
+ * split rows' task partials of either side and (K + 1) rows of per-workgroup dot partials (f64) */
+int64_t sngnn_prop_workspace_bytes(const sngnn_graph_t *g, int C, int K);
+/*
+ * Replaces: models.py:1191-1208 - GPR_prop.forward after gcn_norm, hidden = sum_k gamma_k A^^k x (K propagate
+ * calls with a 4-byte norm per edge and `hidden = hidden + gamma * x`, about five [N, C] passes per hop) - as K
+ * hops in Horner form: h_K = gamma_K x, h_k = gamma_k x + A^ h_{k+1}, out = h_0; per hop the gather, one read of
+ * x and one store.
+ *   x      dev f32 [N, C]     rows aligned to 4 * vec bytes (vec = 4, 2, 1 for C % 4 == 0, C % 2 == 0, odd C)
+ *   gamma  dev f32 [K + 1]    the coefficients rounded to fp32 (the parameter itself is float64: torch rounds a
+ *                             0-dim float64 factor of an fp32 tensor the same way); K >= 1
+ *   dinv   dev f32 [N]        sngnn_prop_dinv's output
+ *   out    dev f32 [N, C]
+ */
+int sngnn_prop_gpr_forward(const sngnn_graph_t *g, const float *x, const float *gamma, int K, int C,
+                           const float *dinv, float *out, void *workspace, void *stream);
+/*
+ * Replaces: autograd through models.py:1200-1204 (K saved iterates [N, C] and K transposed propagations).  Only
+ * x is read: the power form on the transpose, t_0 = grad_out, t_{k+1} = A^T t_k,
+ *   grad_x = sum_k gamma_k t_k   (accumulated in place by the hops' epilogues),
+ *   grad_gamma_k = <t_k, x>      dev f64 [K + 1] - per-workgroup partial dots in double from the same launches,
+ *                                added by one reducer launch in a fixed order: the same bits on every run.
+ * grad_x (dev f32 [N, C]) or grad_gamma may be NULL (not wanted).
+ */
+int sngnn_prop_gpr_backward(const sngnn_graph_t *g, const float *grad_out, const float *x, const float *gamma,
+                            int K, int C, const float *dinv, float *grad_x, double *grad_gamma,
+                            void *workspace, void *stream);
+/*
+ * Replaces: PyG's APPNP.forward as models.py:1033 + 1048 use it (K, alpha; no dropout, no cache): x_0 = h,
+ * x_{k+1} = (1 - alpha) A^ x_k + alpha h, out = x_K; and with transpose != 0 its autograd, the same recurrence on
+ * A^T from h = grad_out (r <- alpha g + (1 - alpha) A^T r): nothing is saved by the forward.
+ *   h      dev f32 [N, C]
+ *   coef   dev f32 [2]       (alpha, 1 - alpha), each rounded to fp32
+ */
+int sngnn_prop_appnp(const sngnn_graph_t *g, const float *h, const float *coef, int K, int C, const float *dinv,
+                     int transpose, float *out, void *workspace, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -28,8 +28,7 @@ SIGNATURES = {
     "sngnn_last_error": (C.c_char_p, []),
     "sngnn_build_info": (C.c_char_p, []),
     "sngnn_graph_create": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, C.POINTER(_vp)]),
-    "sngnn_graph_create_partition": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp,
-                                            C.POINTER(_vp)]),
+    "sngnn_graph_create_partition": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, C.POINTER(_vp)]),
     "sngnn_graph_destroy": (None, [_vp]),
     "sngnn_graph_num_nodes": (_i64, [_vp]),
     "sngnn_graph_num_total_nodes": (_i64, [_vp]),
@@ -45,19 +44,16 @@ SIGNATURES = {
     "sngnn_normalize_rows": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "sngnn_filter_row_bytes": (_i64, [_i32]),
     "sngnn_normalize_rows_filter": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
-    "sngnn_agg_forward_prepared": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _vp]),
+    "sngnn_agg_forward_prepared": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_forward_epilogue": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sngnn_agg_forward_prepared_epilogue": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
-                                                   _vp]),
+    "sngnn_agg_forward_prepared_epilogue": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_filter_enable": (_i32, [_i32]),
     "sngnn_filter_wanted": (_i32, [_vp, _i32, _i32, _f32]),
     "sngnn_agg_forward_rows": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_tuning_set": (_i32, [_i32, _i32]),
     "sngnn_last_forward_finalize_workgroups": (_i32, []),
     "sngnn_filter_pair_scores": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _vp]),
-    "sngnn_agg_forward_normalized": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp]),
+    "sngnn_agg_forward_normalized": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_backward_topk": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_agg_kept_bits_supported": (_i32, [_vp, _i32, _i32]),
@@ -82,8 +78,7 @@ SIGNATURES = {
     "sngnn_blend_backward_epilogue": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_ggcn_transition_workspace_bytes": (_i64, []),
     "sngnn_ggcn_transition_forward": (_i32, [_vp, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp]),
-    "sngnn_ggcn_transition_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
-                                              _vp]),
+    "sngnn_ggcn_transition_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_bn_train_workspace_bytes": (_i64, [_i32]),
     "sngnn_bn_train_forward": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _f32, _vp, _f32] + [_vp] * 5),
     "sngnn_bn_train_backward": (_i32, [_vp, _vp, _vp, _i64, _i32] + [_vp] * 4 + [_f32, _vp, _f32] + [_vp] * 6),
@@ -94,6 +89,11 @@ SIGNATURES = {
     "sngnn_weighted_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_weighted_scatter_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_pair_dot_rows": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "sngnn_prop_dinv": (_i32, [_vp, _vp, _vp]),
+    "sngnn_prop_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "sngnn_prop_gpr_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_prop_gpr_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_prop_appnp": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .batchnorm import _BatchNormAct, batch_norm_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
 from .graph import Graph
+from .prop import appnp_propagate, gpr_propagate  # noqa: F401  (csrc/prop.hip)
 
 
 # storage types of the half path (sngnn_agg_forward_half / sngnn_agg_backward_half, sngnn_attn_*_half,

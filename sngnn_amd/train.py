@@ -79,9 +79,12 @@ def train(model, data, optimizer, epochs: int, patience: int, log=None) -> Dict:
 
 def check_float32(model, x: torch.Tensor, what: str) -> None:
     """Captured epochs and replica batches run float32 models only (their fused launches - lin's epilogue, the head,
-    the kept bits - have no half form): a TypeError that names the dtype for a model cast to float16 / bfloat16."""
+    the kept bits - have no half form): a TypeError that names the dtype for a model cast to float16 / bfloat16.
+    A model may name parameters it keeps in float64 in a ``float64_parameters`` attribute (GPRGNN: ``prop1.temp``, as
+    in the reference); every other parameter, and every parameter of a model without the attribute, must be float32."""
+    wide = getattr(model, "float64_parameters", ())
     for name, p in model.named_parameters():
-        if p.dtype != torch.float32:
+        if p.dtype != torch.float32 and not (p.dtype == torch.float64 and name in wide):
             raise TypeError(f"{what} needs a float32 model: parameter {name} is {p.dtype} "
                             "(train a half model with the eager train())")
     if x.dtype != torch.float32:
