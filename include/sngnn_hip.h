@@ -624,6 +624,60 @@ int sngnn_prop_gpr_backward(const sngnn_graph_t *g, const float *grad_out, const
 int sngnn_prop_appnp(const sngnn_graph_t *g, const float *h, const float *coef, int K, int C, const float *dinv,
                      int transpose, float *out, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Graph attention (GAT): csrc/gat.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * PyG 2.0.4's GATConv after its linear map, for xp = lin_src(x) viewed as [N, H, C] (H heads of C channels):
+ *     a_src[n,h] = <xp[n,h,:], att_src[h,:]>,  a_dst[n,h] = <xp[n,h,:], att_dst[h,:]>
+ *     per in-edge e = (j -> i) and head h:  a_e = leaky_relu(a_src[j,h] + a_dst[i,h], negative_slope)
+ *     alpha_e = exp(a_e - max_i) / (sum_i exp(a - max_i) + 1e-16),   out[i,h,:] = sum_e alpha_e xp[j,h,:]
+ * on the edge list of add_self_loops after remove_self_loops: the graph built with add_loops = 1, remove_loops =
+ * SNGNN_LOOPS_REPLACE, unpartitioned (SNGNN_EINVAL otherwise).  Every row has its loop, so the sum is at least 1 and
+ * the 1e-16 vanishes in fp32.  Limits: 1 <= H <= 16, C >= 1, H * C <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE otherwise).
+ * All rows are dev f32, dense, 16-byte aligned.  Row classes of the other gather kernels (lane group up to 16
+ * in-edges, one wave up to 128, 128-edge tasks + a finalize for split rows), heads on the grid's second dimension;
+ * fixed summation order, no floating-point atomics, no host synchronisation.
+ */
+/* bytes of device workspace of sngnn_gat_forward / sngnn_gat_backward: the split rows' task partials [tasks, H, C]
+ * and two scalars per task and head, the backward's records [E', H, 2], grad_a_src and grad_a_dst [N, H] and the
+ * per-workgroup partials of grad_att (f64); 0 outside the limits */
+int64_t sngnn_gat_workspace_bytes(const sngnn_graph_t *g, int H, int C);
+/*
+ * Replaces: (x_src * att_src).sum(-1), (x_dst * att_dst).sum(-1) (gat_conv.py:197-198) - both from one read of xp,
+ * each score's C products summed in double and rounded once.
+ *   xp       dev f32 [N, H * C]      att_src, att_dst  dev f32 [H * C]      a_src, a_dst  dev f32 [N, H] (out)
+ */
+int sngnn_gat_scores(const float *xp, const float *att_src, const float *att_dst, int64_t N, int H, int C,
+                     float *a_src, float *a_dst, void *stream);
+/*
+ * Replaces: GATConv.propagate - the gathers of alpha_j / alpha_i and x_j, leaky_relu, PyG's softmax (scatter max,
+ * exp, scatter sum, division) and the weighted scatter-add: [E', H] and [E', H, C] intermediates.  Pass one settles
+ * a row's maximum m and sum l per head from a 4-byte gather per edge and head; pass two gathers each head slice
+ * once, weighted by exp(a_e - m), and divides by l in the store.  Split rows: every task writes its partial row,
+ * m_t and l_t; the finalize merges them in task order, m = max m_t, l = sum l_t exp(m_t - m),
+ * out = (sum_t exp(m_t - m) partial_t) / l.
+ *   out      dev f32 [N, H * C]
+ *   ml       dev f32 [2, N, H]       m then l per row and head: with out, all the backward needs saved
+ */
+int sngnn_gat_forward(const sngnn_graph_t *g, const float *xp, const float *a_src, const float *a_dst, int H, int C,
+                      float negative_slope, float *out, float *ml, void *workspace, void *stream);
+/*
+ * Replaces: autograd through the sequence above and through the two score products.  With G = grad_out:
+ *   pass T, in-edges:   t_e = <G[i,h], xp[j,h]>, dot = <G[i,h], out[i,h]>, ds_e = alpha_e (t_e - dot),
+ *                       da_e = ds_e * (a_src[j,h] + a_dst[i,h] > 0 ? 1 : negative_slope),
+ *                       grad_a_dst[i,h] = sum_e da_e; {alpha_e, da_e} stored at the edge's CSC position
+ *   pass S, out-edges:  grad_xp[j,h,:] = sum_e alpha_e G[i,h,:] + grad_a_src[j,h] att_src[h,:]
+ *                                        + grad_a_dst[j,h] att_dst[h,:],   grad_a_src[j,h] = sum_e da_e
+ *   grad_att [2, H * C] (src then dst): grad_att_src[h,c] = sum_j grad_a_src[j,h] xp[j,h,c], dst alike -
+ *                       per-workgroup partials in double added by one reducer launch in a fixed order.
+ * grad_xp (dev f32 [N, H * C]) or grad_att may be NULL (not wanted).
+ */
+int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out, const float *xp, const float *out,
+                       const float *a_src, const float *a_dst, const float *ml, const float *att_src,
+                       const float *att_dst, int H, int C, float negative_slope, float *grad_xp, float *grad_att,
+                       void *workspace, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -4,6 +4,7 @@ aggregation path behind the reference's own nn.Module API.
 The aggregation runs in hand-written HIP (libsngnn_hip.so, C ABI in
 include/sngnn_hip.h); there is no CPU fallback."""
 from .conv import AGNNConv, SNConv, SNConv_plus, SNConv_plus_plus
+from .gatnet import GAT, GATConv
 from .ggcn import GGCN, GGCNlayer_SP
 from .gpr import APPNP, APPNP_Net, GPR_prop, GPRGNN, MLP
 from .models import AGNN, SNGNN, SNGNN_Plus, SNGNN_Plus_Plus
@@ -11,4 +12,4 @@ from .synth import Data
 
 __all__ = ["SNConv", "SNConv_plus", "SNConv_plus_plus", "SNGNN", "SNGNN_Plus",
            "SNGNN_Plus_Plus", "AGNNConv", "AGNN", "GGCNlayer_SP", "GGCN", "MLP", "GPR_prop",
-           "GPRGNN", "APPNP", "APPNP_Net", "Data"]
+           "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "Data"]

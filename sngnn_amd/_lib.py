@@ -25,15 +25,12 @@ _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
 # name -> (restype, argtypes); mirrors include/sngnn_hip.h one to one
 SIGNATURES = {
-    "sngnn_last_error": (C.c_char_p, []),
-    "sngnn_build_info": (C.c_char_p, []),
+    "sngnn_last_error": (C.c_char_p, []), "sngnn_build_info": (C.c_char_p, []),
     "sngnn_graph_create": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, C.POINTER(_vp)]),
     "sngnn_graph_create_partition": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, C.POINTER(_vp)]),
     "sngnn_graph_destroy": (None, [_vp]),
-    "sngnn_graph_num_nodes": (_i64, [_vp]),
-    "sngnn_graph_num_total_nodes": (_i64, [_vp]),
-    "sngnn_graph_row_offset": (_i64, [_vp]),
-    "sngnn_graph_num_edges": (_i64, [_vp]),
+    "sngnn_graph_num_nodes": (_i64, [_vp]), "sngnn_graph_num_total_nodes": (_i64, [_vp]),
+    "sngnn_graph_row_offset": (_i64, [_vp]), "sngnn_graph_num_edges": (_i64, [_vp]),
     "sngnn_graph_max_in_degree": (_i64, [_vp]),
     "sngnn_graph_src_min": (_i64, [_vp]),
     "sngnn_graph_num_fused_nodes": (_i64, [_vp]),
@@ -94,6 +91,9 @@ SIGNATURES = {
     "sngnn_prop_gpr_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_prop_gpr_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_prop_appnp": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "sngnn_gat_workspace_bytes": (_i64, [_vp, _i32, _i32]), "sngnn_gat_scores": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "sngnn_gat_forward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "sngnn_gat_backward": (_i32, [_vp] * 9 + [_i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),
@@ -123,8 +123,7 @@ SIGNATURES = {
     "sngnn_replica_wgrad_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "sngnn_replica_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_replica_head_workspace_bytes": (_i64, [_i32]),
-    "sngnn_replica_head_nll": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp,
-                                      _vp]),
+    "sngnn_replica_head_nll": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_replica_blend_workspace_bytes": (_i64, [_i32]),
     "sngnn_replica_blend_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "sngnn_replica_blend_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .batchnorm import _BatchNormAct, batch_norm_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
+from .gat import gat_propagate  # noqa: F401  (csrc/gat.hip)
 from .graph import Graph
 from .prop import appnp_propagate, gpr_propagate  # noqa: F401  (csrc/prop.hip)
 
