@@ -1,5 +1,6 @@
 // C-ABI entry of the aggregation backward (kernels: agg_bwd_impl.h).
 #include "agg_bwd_impl.h"
+#include "entry.h"
 
 using namespace sngnn;
 
@@ -70,35 +71,16 @@ static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const fl
     if (g->Ntot == 0) return SNGNN_OK;
     SN_REQUIRE(h && grad_h && workspace && (grad_out || g->N == 0), SNGNN_EINVAL, "NULL argument");
     RowCfg cfg;
-    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL,
-               "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    const uintptr_t al = (uintptr_t)cfg.vec * (dtype != 0 ? 2 : 4);     // (half rows: 2 bytes a value)
-    SN_REQUIRE((uintptr_t)h % al == 0 && (uintptr_t)grad_out % al == 0 && (uintptr_t)grad_h % al == 0,
-               SNGNN_EINVAL, "h/grad_out/grad_h must be aligned to the row vector width");
+    if (int rc = check_rows(C, dtype, {h, grad_out, grad_h}, cfg)) return rc;
+    const BwdLayout L = bwd_layout(g, C, false);
     BwdArgs a;
-    a.h = h; a.gout = grad_out; a.wsel = wsel;
-    a.C = C; a.N = (int)g->N; a.Ntot = (int)g->Ntot; a.row_off = (int)g->row_off;
-    a.rowptr = g->rowptr; a.col = g->col; a.rperm = g->rperm; a.rdesc = g->rdesc; a.sdesc = g->sdesc;
-    a.cscptr = g->cscptr; a.csc_eid = g->csc_eid; a.csc_dst = g->csc_dst; a.csc_pos = g->csc_pos;
-    a.sperm = g->sperm;
-    // workspace layout (sngnn_graph_workspace_bytes): [2 floats per edge: the kept-bit mask
-    // lives in its first words; the attention mode keeps records there] | dnT | partT | partS
-    float *ws = (float *)workspace;
+    bind_bwd_graph(g, C, L, workspace, a);
+    a.h = h; a.gout = grad_out; a.wsel = wsel; a.grad_h = grad_h;
+    // (the kept-bit mask lives in the first words of the records' region; the attention mode keeps records there)
     a.wd = nullptr; a.rec_dot = nullptr;
-    a.kmask = (unsigned *)ws;
+    a.kmask = (unsigned *)((char *)workspace + L.rec);
     a.kmask_words = (g->Ep + 31) / 32;
-    a.Ep = g->Ep;
     a.inv_deg = g->inv_deg;
-    const size_t ds_len = (2 * (size_t)g->Ep + 3) / 4 * 4;  // keep rows 16-byte aligned
-    a.dnT = ws + ds_len;
-    a.partT = a.dnT + (size_t)g->N * C;
-    a.partS = a.partT + (size_t)g->n_tasks * C;
-    a.grad_h = grad_h;
-    a.n_split = g->n_split; a.n_med_end = g->rows_gt(SMALL_T); a.n_tasks = g->n_tasks;
-    a.task_slot = g->task_slot; a.task_chunk = g->task_chunk; a.split_task0 = g->split_task0;
-    a.n_ssplit = g->n_ssplit; a.n_smed_end = g->srcs_gt(SMALL_T); a.n_stasks = g->n_stasks;
-    a.stask_slot = g->stask_slot; a.stask_chunk = g->stask_chunk; a.ssplit_task0 = g->ssplit_task0;
-    a.nbA = a.nbB = a.nbC = 0;
     // The node-centric path pays when most nodes are FUSED work items (small both as target and as
     // source: four nodes per wave, both passes in one go) - 95 % at arxiv's degree law, where it wins
     // at every size tried (x1 .. x32: 1.2 M .. 37 M edges, 60 vs 77 us .. 2.26 vs 2.72 ms).  Where
@@ -113,18 +95,5 @@ static int backward_impl(const sngnn_graph_t *g, const float *h, int C, const fl
     a.n_fused = g->n_fused; a.n_trest = g->n_trest;
     a.kbits = kbits; a.csc_bit = g->csc_bit; a.kb_wbase = (int)g->kb_wbase; a.kb_tbase = (int)g->kb_tbase;
     a.s_small_end = a.mode == 0 ? g->srcs_gt(SMALL_T - 1) : (int)g->Ntot;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype != 0) {
-        const bool f16 = dtype == SNGNN_DTYPE_F16;
-        switch (cfg.vec) {
-        case 1: return f16 ? launch_agg_bwd_f16_v1(cfg, a, st) : launch_agg_bwd_bf16_v1(cfg, a, st);
-        case 2: return f16 ? launch_agg_bwd_f16_v2(cfg, a, st) : launch_agg_bwd_bf16_v2(cfg, a, st);
-        default: return f16 ? launch_agg_bwd_f16_v4(cfg, a, st) : launch_agg_bwd_bf16_v4(cfg, a, st);
-        }
-    }
-    switch (cfg.vec) {
-    case 1: return launch_agg_bwd_v1(cfg, a, st);
-    case 2: return launch_agg_bwd_v2(cfg, a, st);
-    default: return launch_agg_bwd_v4(cfg, a, st);
-    }
+    return SNGNN_LAUNCH_VEC(launch_agg_bwd_vec, cfg, dtype, a, (hipStream_t)stream);
 }

@@ -1,12 +1,5 @@
 // Instantiates the half path's aggregation backward for bf16 rows read 2 value(s) per lane
-// (agg_bwd_impl.h: LaunchBwdHalf).
+// (agg_bwd_impl.h: SNGNN_AGG_BWD_TU).
 #include "agg_bwd_impl.h"
 
-namespace sngnn {
-
-int launch_agg_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(LaunchBwdHalf<__hip_bfloat16>::run, 2, cfg, a, st)
-}
-
-}  // namespace sngnn
+SNGNN_AGG_BWD_TU(__hip_bfloat16, 2)

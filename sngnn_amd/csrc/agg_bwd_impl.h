@@ -988,22 +988,15 @@ template <int VEC, int G, int R, typename S = float> int launch_agg_bwd(const Bw
     return SNGNN_OK;
 }
 
-int launch_agg_bwd_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-// the half path (sngnn_agg_backward_half: h, gout and grad_h stored as S), one translation unit per storage type
-// and VEC (agg_bwd_f16_v*.hip, agg_bwd_bf16_v*.hip)
-template <typename S> struct LaunchBwdHalf {
-    template <int VEC, int G, int R> static int run(const BwdArgs &a, hipStream_t st)
-    {
-        return launch_agg_bwd<VEC, G, R, S>(a, st);
-    }
-};
-int launch_agg_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_agg_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+// defined one per translation unit: storage type S (float, or the half path - sngnn_agg_backward_half: h, gout and
+// grad_h stored as S) x VEC values per lane (agg_bwd[_f16|_bf16]_v*.hip)
+template <typename S, int VEC> int launch_agg_bwd_vec(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 
 }  // namespace sngnn
+
+#define SNGNN_AGG_BWD_TU(S, VEC)                                                                                       \
+    template <> int sngnn::launch_agg_bwd_vec<S, VEC>(const RowCfg &cfg, const BwdArgs &a, hipStream_t st)             \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_agg_bwd, VEC, S, cfg, a, st)                                                         \
+    }
+

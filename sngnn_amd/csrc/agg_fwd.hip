@@ -1,6 +1,7 @@
 // C-ABI entries of the fused aggregation forward (see agg_fwd_impl.h for the kernels).
 #include <atomic>
 #include "agg_fwd_impl.h"
+#include "entry.h"
 
 using namespace sngnn;
 
@@ -49,11 +50,9 @@ static __global__ void k_fill_sel(int32_t *__restrict__ src, float *__restrict__
 static int normalize_dispatch(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm,
                               void *filt, hipStream_t st)
 {
-    switch (cfg.vec) {
-    case 1: return launch_normalize_v1(cfg, h, rows, C, n, nrm, filt, st);
-    case 2: return launch_normalize_v2(cfg, h, rows, C, n, nrm, filt, st);
-    default: return launch_normalize_v4(cfg, h, rows, C, n, nrm, filt, st);
-    }
+    return dispatch_vec(cfg, [&](auto vec) {
+        return launch_normalize_vec<float, decltype(vec)::value>(cfg, h, rows, C, n, nrm, filt, st);
+    });
 }
 
 // wave rows shorter than this score their fp32 rows directly: two dependent round trips for a short row cost more than
@@ -117,9 +116,7 @@ extern "C" int sngnn_normalize_rows_filter(const float *h, int64_t rows, int C, 
     SN_REQUIRE(rows >= 0, SNGNN_EINVAL, "negative row count");
     SN_REQUIRE(rows == 0 || (h && n && nrm), SNGNN_EINVAL, "h/n/nrm is NULL");
     RowCfg cfg;
-    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL, "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    SN_REQUIRE(((uintptr_t)h % (cfg.vec * 4)) == 0 && ((uintptr_t)n % (cfg.vec * 4)) == 0, SNGNN_EINVAL,
-               "h/n must be aligned to the row vector width");
+    if (int rc = check_rows(C, 0, {h, n}, cfg)) return rc;
     SN_REQUIRE(filt == nullptr || filter_row_bytes(C) > 0, SNGNN_EINVAL,
                "no filter rows for this C (sngnn_filter_row_bytes(C) == 0)");
     SN_REQUIRE(((uintptr_t)filt % 16) == 0, SNGNN_EINVAL, "filt must be 16-byte aligned");
@@ -171,20 +168,43 @@ extern "C" int sngnn_filter_pair_scores(const void *filt, int C, const int64_t *
     return SNGNN_OK;
 }
 
-// everything after the unit rows exist
-static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const float *n, const float *nrm,
-                              const void *filt, int C, int top_k, float thr, float *out, float *wsel, float *inv_norm,
-                              int32_t *sel_src, float *sel_w, void *scratch, hipEvent_t *ev, hipStream_t st,
-                              const uint8_t *row_flag = nullptr, int row_want = 0, const sngnn_epilogue_t *epi = nullptr,
-                              int dtype = 0)
-{
-    if (top_k > (1 << 20)) top_k = 1 << 20;     // more than any row can use
+// One forward call as its entry describes it (the seven extern "C" forwards below fill this and run it).
+struct FwdCall {
+    const sngnn_graph_t *g;
+    const void *rows;               // raw rows h (fp32, or dtype's half type); with `prepared` the caller's unit rows
+    int dtype = 0;                  // 0 = fp32 rows and out, else SNGNN_DTYPE_F16 / _BF16 (always scored on the fly)
+    bool prepared = false;          // the caller holds the unit rows: rows | nrm | (optional) filt
+    const float *nrm = nullptr;
+    const void *filt = nullptr;
+    bool by_rows = false;           // sngnn_agg_forward_rows: only the rows with row_flag == row_want
+    const uint8_t *row_flag = nullptr;
+    int row_want = 0;
+    int C, top_k;
+    float thr;
+    const sngnn_epilogue_t *epi = nullptr;
+    void *out;
+    float *wsel, *inv_norm;
+    int32_t *sel_src = nullptr;
+    float *sel_w = nullptr;
+    void *workspace, *stream;
+};
 
-    if (sel_src && top_k > 0 && row_flag == nullptr) {
+// everything after the unit rows exist (nrm == NULL: n holds the raw rows and the kernels score on the fly)
+static int launch_forward(const FwdCall &c, const RowCfg &cfg, const float *n, const float *nrm, const void *filt,
+                          hipEvent_t *ev)
+{
+    const sngnn_graph_t *g = c.g;
+    const sngnn_epilogue_t *epi = c.epi;
+    const int C = c.C;
+    const float thr = c.thr;
+    hipStream_t st = (hipStream_t)c.stream;
+    const int top_k = std::min(c.top_k, 1 << 20);     // more than any row can use
+
+    if (c.sel_src && top_k > 0 && c.row_flag == nullptr) {
         // (a kernel, not hipMemsetAsync: inside a captured HIP graph a memset node was seen to
         // race with the kernel nodes behind it on this stack - see agg_bwd_impl.h)
         const int64_t nw = g->N * (int64_t)top_k;
-        k_fill_sel<<<(int)std::min<int64_t>((nw + 255) / 256, 2048), 256, 0, st>>>(sel_src, sel_w, nw);
+        k_fill_sel<<<(int)std::min<int64_t>((nw + 255) / 256, 2048), 256, 0, st>>>(c.sel_src, c.sel_w, nw);
     }
 
     FwdArgs a;
@@ -203,13 +223,13 @@ static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const f
     // the margin on the constant term.
     a.delta = (float)(4 * C + 32) * 5.9604644775390625e-8f;
     a.role_mask = g_role_mask;
-    a.row_flag = row_flag; a.row_want = row_want;
+    a.row_flag = c.row_flag; a.row_want = c.row_want;
     a.epi_flags = 0; a.epi_bias = nullptr; a.epi_keep = nullptr; a.epi_seed = nullptr; a.epi_p = 0.f; a.epi_scale = 1.0f;
     a.head_y = nullptr; a.head_sel = nullptr; a.head_part = nullptr; a.head_flags = 0; a.head_nmain = 0;
     a.head_scale = a.head_scale_b = 0.f; a.head_out = nullptr;
     a.kbits = nullptr; a.kb_wbase = (int)g->kb_wbase; a.kb_tbase = (int)g->kb_tbase;
     if (epi && epi->kept_bits) {
-        SN_REQUIRE(sngnn::kept_bits_path(g, top_k) && row_flag == nullptr && nrm != nullptr, SNGNN_EINVAL,
+        SN_REQUIRE(sngnn::kept_bits_path(g, top_k) && c.row_flag == nullptr && nrm != nullptr, SNGNN_EINVAL,
                    "no kept-bit path for this graph / top_k (sngnn_agg_kept_bits_supported)");
         a.kbits = (unsigned *)epi->kept_bits;
     }
@@ -222,10 +242,10 @@ static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const f
         SN_REQUIRE(epi->head_sets == 1 || epi->head_sets == 2, SNGNN_EINVAL, "head_sets must be 1 or 2");
         SN_REQUIRE((epi->head_out_mode == 1 || epi->head_out_mode == 2) && (epi->head_out_mode != 2 || epi->head_sets == 1),
                    SNGNN_EINVAL, "head_out_mode: 1 logits, 2 gradient (one split only)");
-        SN_REQUIRE(out != nullptr, SNGNN_EINVAL, "out is NULL");
+        SN_REQUIRE(c.out != nullptr, SNGNN_EINVAL, "out is NULL");
         SN_REQUIRE(!epi->relu && epi->keep == nullptr && epi->seed == nullptr, SNGNN_EINVAL,
                    "the head follows the LAST layer: no relu / dropout with it");
-        SN_REQUIRE(row_flag == nullptr && sel_src == nullptr, SNGNN_EINVAL,
+        SN_REQUIRE(c.row_flag == nullptr && c.sel_src == nullptr, SNGNN_EINVAL,
                    "the head epilogue covers all rows of a call and emits no selection lists");
         a.head_y = epi->head_y; a.head_sel = epi->head_sel;
         a.head_part = (float *)epi->head_workspace; a.head_out = epi->head_metrics;
@@ -248,20 +268,19 @@ static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const f
     a.rperm = stream_small ? g->rperm_b : g->rperm;
     a.rdesc = stream_small ? g->rdesc_b : g->rdesc;
     a.k = top_k < 0 ? -1 : top_k; a.thr = thr;
-    a.out = out; a.wsel = wsel; a.inv_norm = inv_norm;
-    a.sel_src = top_k > 0 ? sel_src : nullptr; a.sel_w = top_k > 0 ? sel_w : nullptr;
-    a.n_split = g->n_split;
-    a.n_med_end = g->rows_gt(SMALL_T);
-    a.n_tasks = g->n_tasks;
-    a.task_slot = g->task_slot; a.task_chunk = g->task_chunk;
+    a.out = (float *)c.out; a.wsel = c.wsel; a.inv_norm = c.inv_norm;
+    a.sel_src = top_k > 0 ? c.sel_src : nullptr; a.sel_w = top_k > 0 ? c.sel_w : nullptr;
+    bind_side(g, false, a);
     a.task_order = g->task_order;
-    a.split_soff = g->split_soff; a.split_task0 = g->split_task0;
-    a.scores = (float *)scratch;
-    a.partial = a.scores ? a.scores + (g->split_edges + 3) / 4 * 4 : nullptr;   // 16-B aligned rows
-    a.cand_key = a.partial ? (unsigned long long *)(a.partial + ((size_t)g->n_tasks * C + 3) / 4 * 4)
-                           : nullptr;
-    a.cand_src = a.cand_key ? (int32_t *)(a.cand_key + (size_t)g->n_tasks * CAND_MAX_K) : nullptr;
-    a.fin_done = a.cand_src ? (unsigned long long *)(a.cand_src + (size_t)g->n_tasks * CAND_MAX_K) : nullptr;   // 8-byte aligned
+    a.split_soff = g->split_soff;
+    // the split rows' scratch (a prepared call on a graph without split rows may bring no workspace)
+    const FwdLayout L = fwd_layout(g, C);
+    char *ws = (char *)c.workspace;
+    a.scores = ws ? (float *)(ws + L.scores) : nullptr;
+    a.partial = ws ? (float *)(ws + L.partial) : nullptr;
+    a.cand_key = ws ? (unsigned long long *)(ws + L.cand_key) : nullptr;
+    a.cand_src = ws ? (int32_t *)(ws + L.cand_src) : nullptr;
+    a.fin_done = ws ? (unsigned long long *)(ws + L.fin_done) : nullptr;
     a.fin_nonce = 0ull; a.main_blocks = 0; a.n_edges = (long long)g->Ep;
     a.k_magic = top_k >= 2 ? (unsigned)(0xFFFFFFFFu / (unsigned)top_k + 1u) : 0u;
     const int max_split = g->n_split ? g->rdeg[0] : 0;
@@ -274,52 +293,22 @@ static int forward_normalized(const sngnn_graph_t *g, const RowCfg &cfg, const f
                                   : (top_k < 0 ? g->rows_gt((int64_t)16 * CHUNK) : 0);
     a.lowbits = 1;
     while ((1ll << a.lowbits) < g->max_in_deg && a.lowbits < 31) ++a.lowbits;
-    if (dtype != 0) {
-        // the half path (sngnn_agg_forward_half: n = the raw half rows, nrm == NULL, no epilogue / head / kept bits)
-        const bool f16 = dtype == SNGNN_DTYPE_F16;
-        switch (cfg.vec) {
-        case 1: return f16 ? launch_agg_fwd_f16_v1(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v1(cfg, a, max_split, ev, st);
-        case 2: return f16 ? launch_agg_fwd_f16_v2(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v2(cfg, a, max_split, ev, st);
-        default: return f16 ? launch_agg_fwd_f16_v4(cfg, a, max_split, ev, st) : launch_agg_fwd_bf16_v4(cfg, a, max_split, ev, st);
-        }
-    }
     if (head) {
         SN_REQUIRE(g->n_split == 0 || a.use_cand, SNGNN_EINVAL,
                    "no head epilogue: this graph's biggest row takes the scratch-score finalize (sngnn_agg_head_supported)");
-        return launch_agg_fwd_v4(cfg, a, max_split, ev, st);      // (the plain kernels: the head rides in the second launch)
+        // (the plain kernels: the head rides in the second launch)
+        return launch_agg_fwd_vec<float, 4>(cfg, a, max_split, ev, st);
     }
     if (a.epi_flags != 0) {
         SN_REQUIRE(cfg.vec == 4, SNGNN_EINVAL, "the store epilogue needs C % 4 == 0 (16-byte rows)");
         return launch_agg_fwd_epi_v4(cfg, a, max_split, ev, st);
     }
-    switch (cfg.vec) {
-    case 1: return launch_agg_fwd_v1(cfg, a, max_split, ev, st);
-    case 2: return launch_agg_fwd_v2(cfg, a, max_split, ev, st);
-    default: return launch_agg_fwd_v4(cfg, a, max_split, ev, st);
-    }
+    // (the half path: n = the raw half rows, nrm == NULL, no epilogue / head / kept bits)
+    return SNGNN_LAUNCH_VEC(launch_agg_fwd_vec, cfg, c.dtype, a, max_split, ev, st);
 }
 
-static int check_forward_args(const sngnn_graph_t *g, const float *rows, int C, int top_k, const float *out,
-                              const int32_t *sel_src, const float *sel_w, RowCfg &cfg)
-{
-    SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
-    SN_REQUIRE(g->N == 0 || (rows != nullptr && out != nullptr), SNGNN_EINVAL, "h/out is NULL");
-    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL,
-               "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    SN_REQUIRE(((uintptr_t)rows % (cfg.vec * 4)) == 0 && ((uintptr_t)out % (cfg.vec * 4)) == 0,
-               SNGNN_EINVAL, "h/out must be aligned to the row vector width");
-    SN_REQUIRE((sel_src == nullptr) == (sel_w == nullptr), SNGNN_EINVAL,
-               "sel_src and sel_w go together");
-    SN_REQUIRE(sel_src == nullptr || top_k >= 0, SNGNN_EINVAL, "sel_src needs top_k >= 0");
-    return SNGNN_OK;
-}
-
-// the filter region of the workspace, and whether a call uses it: rows that rank (in-degree >
-// top_k) above the small class must exist, otherwise nothing would read the table
-static void *ws_filter(void *workspace, int64_t Ntot, int C)
-{
-    return (char *)workspace + (Ntot * (int64_t)C * 4 + 255) / 256 * 256 + (Ntot * 4 + 255) / 256 * 256;
-}
+// whether a call uses the filter region of the workspace: rows that rank (in-degree > top_k) above the small
+// class must exist, otherwise nothing would read the table
 static bool use_filter(const sngnn_graph_t *g, int C, int top_k, float thr)
 {
     if (g_filter_mode == 0 || top_k < 0 || filter_row_bytes(C) == 0) return false;
@@ -347,72 +336,92 @@ static bool use_filter(const sngnn_graph_t *g, int C, int top_k, float thr)
     return false;
 }
 
-static int agg_forward_impl(const sngnn_graph_t *g, const float *h, int C, int top_k,
-                            float thr, float *out, float *wsel, float *inv_norm,
-                            int32_t *sel_src, float *sel_w, void *workspace, void *stream, const sngnn_epilogue_t *epi)
+// Checks a call, decides where its unit rows and filter rows come from, and launches it.
+static int run_forward(const FwdCall &c)
 {
+    const sngnn_graph_t *g = c.g;
+    const sngnn_epilogue_t *epi = c.epi;
+    SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
+    SN_REQUIRE(g->N == 0 || (c.rows != nullptr && c.out != nullptr), SNGNN_EINVAL, "h/out is NULL");
     RowCfg cfg;
-    if (int rc = check_forward_args(g, h, C, top_k, out, sel_src, sel_w, cfg)) return rc;
-    if (g->N == 0 && epi != nullptr && epi->head_y != nullptr && epi->head_metrics != nullptr)      // no row: zero metrics
-        return launch_head_reduce(nullptr, 0, 0.f, 0.f, epi->head_sets == 2 ? 2 : 1, 4, epi->head_metrics, (hipStream_t)stream);
-    if (g->N == 0) return SNGNN_OK;
-    SN_REQUIRE(workspace != nullptr, SNGNN_EINVAL, "workspace is NULL");
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t *ev0 = g_prof_on ? g_prof_ev : nullptr;
-    void *scratch0 = (char *)workspace + fwd_table_bytes(g->Ntot, C);
-    if (g_table_mode == 2 || (g_table_mode == 0 && top_k < 0)) {
-        // on the fly: no normalisation pass, no table - the kernels gather h itself (FwdArgs)
-        if (ev0) {
-            SN_HIP(hipEventRecord(ev0[0], st));
-        }
-        return forward_normalized(g, cfg, h, nullptr, nullptr, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w,
-                                  scratch0, ev0 ? ev0 + 1 : nullptr, st, nullptr, 0, epi);
+    if (int rc = check_rows(c.C, c.dtype, {c.rows, c.out}, cfg)) return rc;
+    SN_REQUIRE((c.sel_src == nullptr) == (c.sel_w == nullptr), SNGNN_EINVAL, "sel_src and sel_w go together");
+    SN_REQUIRE(c.sel_src == nullptr || c.top_k >= 0, SNGNN_EINVAL, "sel_src needs top_k >= 0");
+    hipStream_t st = (hipStream_t)c.stream;
+    if (g->N == 0) {        // no row: zero head metrics, nothing else
+        if (epi != nullptr && epi->head_y != nullptr && epi->head_metrics != nullptr)
+            return launch_head_reduce(nullptr, 0, 0.f, 0.f, epi->head_sets == 2 ? 2 : 1, 4, epi->head_metrics, st);
+        return SNGNN_OK;
     }
-    // table mode (sngnn_tuning_set(2, 1)): the normalisation pass first.
-    // workspace: unit rows [Ntot, C] | norms [Ntot] | fp16 filter rows | scratch of the split rows
-    float *n = (float *)workspace;
-    float *nrm = (float *)((char *)workspace + (g->Ntot * (int64_t)C * 4 + 255) / 256 * 256);
-    void *scratch = (char *)workspace + fwd_table_bytes(g->Ntot, C);
-    void *filt = (use_filter(g, C, top_k, thr) && !(epi && epi->no_filter)) ? ws_filter(workspace, g->Ntot, C) : nullptr;
-    hipEvent_t *ev = g_prof_on ? g_prof_ev : nullptr;
+    // raw fp32 rows go through the unit-row table unless the call scores on the fly from h itself: no normalisation
+    // pass, no table - the kernels gather h (FwdArgs).  The half rows always do (knob 2 = 2's form: the table path
+    // would need a unit-row table of the half rows' fp32 values - a pass, and 4 C bytes per row where the rows have 2 C).
+    const bool table = !c.prepared && c.dtype == 0 && !(g_table_mode == 2 || (g_table_mode == 0 && c.top_k < 0));
+    // the filter decision (sngnn_agg_forward_rows leaves it to its caller - sngnn_filter_wanted - who passes the rows
+    // or NULL; a call that scores on the fly has no table to filter)
+    const bool pays = (table || (c.prepared && !c.by_rows)) && use_filter(g, c.C, c.top_k, c.thr);
+    const bool filter = pays && !(epi && epi->no_filter);
+    if (c.by_rows) {
+        // (nrm == NULL: rows holds the RAW rows h and the call scores on the fly, like sngnn_agg_forward)
+        SN_REQUIRE(c.row_flag != nullptr && c.workspace != nullptr, SNGNN_EINVAL, "row_flag/workspace is NULL");
+        SN_REQUIRE(c.nrm != nullptr || c.filt == nullptr, SNGNN_EINVAL, "filter rows go with unit rows + norms");
+    } else if (c.prepared) {
+        SN_REQUIRE(c.nrm != nullptr, SNGNN_EINVAL, "nrm is NULL");
+        SN_REQUIRE(c.workspace != nullptr || (g->n_tasks == 0 && (c.filt != nullptr || !pays)), SNGNN_EINVAL,
+                   "workspace is NULL");
+    } else {
+        SN_REQUIRE(c.workspace != nullptr, SNGNN_EINVAL, "workspace is NULL");
+    }
+    if (c.prepared) {
+        SN_REQUIRE(c.filt == nullptr || filter_row_bytes(c.C) > 0, SNGNN_EINVAL,
+                   "no filter rows for this C (sngnn_filter_row_bytes(C) == 0)");
+        SN_REQUIRE(((uintptr_t)c.filt % 16) == 0, SNGNN_EINVAL, "filt must be 16-byte aligned");
+    }
+    // the same workspace layout for every entry; a prepared call leaves the unit-row region unused
+    const FwdLayout L = fwd_layout(g, c.C);
+    char *ws = (char *)c.workspace;
+    hipEvent_t *ev = (g_prof_on && !c.by_rows) ? g_prof_ev : nullptr;
     if (ev) SN_HIP(hipEventRecord(ev[0], st));
-    for (int rep = 0; rep < (ev ? g_prof_reps : 1); ++rep)
-        if (int rc = normalize_dispatch(cfg, h, g->Ntot, C, n, nrm, filt, st)) return rc;
-    return forward_normalized(g, cfg, n, nrm, filt, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w, scratch,
-                              ev ? ev + 1 : nullptr, st, nullptr, 0, epi);
+    const float *n = (const float *)c.rows, *nrm = c.nrm;
+    const void *filt = c.by_rows ? c.filt : nullptr;
+    if (table) {
+        // (sngnn_tuning_set(2, 1) forces it) the normalisation pass first
+        float *unit = (float *)(ws + L.unit), *norms = (float *)(ws + L.nrm);
+        void *wf = filter ? ws + L.filt : nullptr;
+        for (int rep = 0; rep < (ev ? g_prof_reps : 1); ++rep)
+            if (int rc = normalize_dispatch(cfg, n, g->Ntot, c.C, unit, norms, wf, st)) return rc;
+        n = unit; nrm = norms; filt = wf;
+    } else if (filter) {
+        filt = c.filt;
+        if (!filt) {       // the caller holds no filter rows: one more pass over its unit rows
+            if (int rc = launch_filter_v4(cfg, n, g->Ntot, c.C, ws + L.filt, st)) return rc;
+            filt = ws + L.filt;
+        }
+    }
+    return launch_forward(c, cfg, n, nrm, filt, ev ? ev + 1 : nullptr);
 }
 
 extern "C" int sngnn_agg_forward(const sngnn_graph_t *g, const float *h, int C, int top_k,
                                  float thr, float *out, float *wsel, float *inv_norm,
                                  int32_t *sel_src, float *sel_w, void *workspace, void *stream)
 {
-    return agg_forward_impl(g, h, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w, workspace, stream, nullptr);
+    FwdCall c;
+    c.g = g; c.rows = h; c.C = C; c.top_k = top_k; c.thr = thr; c.out = out; c.wsel = wsel; c.inv_norm = inv_norm;
+    c.sel_src = sel_src; c.sel_w = sel_w; c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
-// The half path: h and out stored as fp16 / bf16, always scored on the fly (knob 2 = 2's form: the table path would
-// need a unit-row table of the half rows' fp32 values - a pass, and 4 C bytes per row where the rows have 2 C).
+// The half path: h and out stored as fp16 / bf16, always scored on the fly.
 extern "C" int sngnn_agg_forward_half(const sngnn_graph_t *g, const void *h, int dtype, int C, int top_k, float thr,
                                       void *out, float *wsel, float *inv_norm, int32_t *sel_src, float *sel_w,
                                       void *workspace, void *stream)
 {
     SN_REQUIRE(dtype == SNGNN_DTYPE_F16 || dtype == SNGNN_DTYPE_BF16, SNGNN_EINVAL,
                "dtype must be SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16");
-    SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
-    SN_REQUIRE(g->N == 0 || (h != nullptr && out != nullptr), SNGNN_EINVAL, "h/out is NULL");
-    RowCfg cfg;
-    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL, "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    SN_REQUIRE(((uintptr_t)h % (cfg.vec * 2)) == 0 && ((uintptr_t)out % (cfg.vec * 2)) == 0, SNGNN_EINVAL,
-               "h/out must be aligned to the row vector width (2 * vec bytes)");
-    SN_REQUIRE((sel_src == nullptr) == (sel_w == nullptr), SNGNN_EINVAL, "sel_src and sel_w go together");
-    SN_REQUIRE(sel_src == nullptr || top_k >= 0, SNGNN_EINVAL, "sel_src needs top_k >= 0");
-    if (g->N == 0) return SNGNN_OK;
-    SN_REQUIRE(workspace != nullptr, SNGNN_EINVAL, "workspace is NULL");
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t *ev = g_prof_on ? g_prof_ev : nullptr;
-    if (ev) SN_HIP(hipEventRecord(ev[0], st));
-    return forward_normalized(g, cfg, (const float *)h, nullptr, nullptr, C, top_k, thr, (float *)out, wsel, inv_norm,
-                              sel_src, sel_w, (char *)workspace + fwd_table_bytes(g->Ntot, C), ev ? ev + 1 : nullptr, st,
-                              nullptr, 0, nullptr, dtype);
+    FwdCall c;
+    c.g = g; c.rows = h; c.dtype = dtype; c.C = C; c.top_k = top_k; c.thr = thr; c.out = out; c.wsel = wsel;
+    c.inv_norm = inv_norm; c.sel_src = sel_src; c.sel_w = sel_w; c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
 extern "C" int64_t sngnn_agg_head_workspace_bytes(const sngnn_graph_t *g)
@@ -443,41 +452,10 @@ extern "C" int sngnn_agg_forward_epilogue(const sngnn_graph_t *g, const float *h
                                           void *workspace, void *stream)
 {
     if (int rc = check_epilogue(epi)) return rc;
-    return agg_forward_impl(g, h, C, top_k, thr, out, wsel, inv_norm, nullptr, nullptr, workspace, stream, epi);
-}
-
-static int agg_forward_prepared_impl(const sngnn_graph_t *g, const float *n, const float *nrm,
-                                     const void *filt, int C, int top_k, float thr, float *out, float *wsel,
-                                     float *inv_norm, int32_t *sel_src, float *sel_w, void *workspace,
-                                     void *stream, const sngnn_epilogue_t *epi)
-{
-    RowCfg cfg;
-    if (int rc = check_forward_args(g, n, C, top_k, out, sel_src, sel_w, cfg)) return rc;
-    if (g->N == 0 && epi != nullptr && epi->head_y != nullptr && epi->head_metrics != nullptr)
-        return launch_head_reduce(nullptr, 0, 0.f, 0.f, epi->head_sets == 2 ? 2 : 1, 4, epi->head_metrics, (hipStream_t)stream);
-    if (g->N == 0) return SNGNN_OK;
-    SN_REQUIRE(nrm != nullptr, SNGNN_EINVAL, "nrm is NULL");
-    SN_REQUIRE(workspace != nullptr || (g->n_tasks == 0 && (filt != nullptr || !use_filter(g, C, top_k, thr))),
-               SNGNN_EINVAL, "workspace is NULL");
-    SN_REQUIRE(filt == nullptr || filter_row_bytes(C) > 0, SNGNN_EINVAL,
-               "no filter rows for this C (sngnn_filter_row_bytes(C) == 0)");
-    SN_REQUIRE(((uintptr_t)filt % 16) == 0, SNGNN_EINVAL, "filt must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    // same workspace layout as sngnn_agg_forward; the unit-row region stays unused
-    void *scratch = workspace ? (char *)workspace + fwd_table_bytes(g->Ntot, C) : nullptr;
-    hipEvent_t *ev = g_prof_on ? g_prof_ev : nullptr;
-    if (ev) { SN_HIP(hipEventRecord(ev[0], st)); }
-    const void *f = nullptr;
-    if (use_filter(g, C, top_k, thr) && !(epi && epi->no_filter)) {
-        f = filt;
-        if (!f) {       // the caller holds no filter rows: one more pass over its unit rows
-            void *wf = ws_filter(workspace, g->Ntot, C);
-            if (int rc = launch_filter_v4(cfg, n, g->Ntot, C, wf, st)) return rc;
-            f = wf;
-        }
-    }
-    return forward_normalized(g, cfg, n, nrm, f, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w, scratch,
-                              ev ? ev + 1 : nullptr, st, nullptr, 0, epi);
+    FwdCall c;
+    c.g = g; c.rows = h; c.C = C; c.top_k = top_k; c.thr = thr; c.epi = epi; c.out = out; c.wsel = wsel;
+    c.inv_norm = inv_norm; c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
 extern "C" int sngnn_agg_forward_prepared(const sngnn_graph_t *g, const float *n, const float *nrm,
@@ -485,8 +463,11 @@ extern "C" int sngnn_agg_forward_prepared(const sngnn_graph_t *g, const float *n
                                           float *inv_norm, int32_t *sel_src, float *sel_w, void *workspace,
                                           void *stream)
 {
-    return agg_forward_prepared_impl(g, n, nrm, filt, C, top_k, thr, out, wsel, inv_norm, sel_src, sel_w, workspace,
-                                     stream, nullptr);
+    FwdCall c;
+    c.g = g; c.rows = n; c.prepared = true; c.nrm = nrm; c.filt = filt; c.C = C; c.top_k = top_k; c.thr = thr;
+    c.out = out; c.wsel = wsel; c.inv_norm = inv_norm; c.sel_src = sel_src; c.sel_w = sel_w;
+    c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
 extern "C" int sngnn_agg_forward_prepared_epilogue(const sngnn_graph_t *g, const float *n, const float *nrm,
@@ -495,27 +476,21 @@ extern "C" int sngnn_agg_forward_prepared_epilogue(const sngnn_graph_t *g, const
                                                    float *inv_norm, void *workspace, void *stream)
 {
     if (int rc = check_epilogue(epi)) return rc;
-    return agg_forward_prepared_impl(g, n, nrm, filt, C, top_k, thr, out, wsel, inv_norm, nullptr, nullptr, workspace,
-                                     stream, epi);
+    FwdCall c;
+    c.g = g; c.rows = n; c.prepared = true; c.nrm = nrm; c.filt = filt; c.C = C; c.top_k = top_k; c.thr = thr;
+    c.epi = epi; c.out = out; c.wsel = wsel; c.inv_norm = inv_norm; c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
 extern "C" int sngnn_agg_forward_rows(const sngnn_graph_t *g, const float *n, const float *nrm, const void *filt,
                                       int C, int top_k, float thr, const uint8_t *row_flag, int row_want,
                                       float *out, float *wsel, float *inv_norm, void *workspace, void *stream)
 {
-    RowCfg cfg;
-    if (int rc = check_forward_args(g, n, C, top_k, out, nullptr, nullptr, cfg)) return rc;
-    if (g->N == 0) return SNGNN_OK;
-    // (nrm == NULL: n holds the RAW rows h and the call scores on the fly, like sngnn_agg_forward)
-    SN_REQUIRE(row_flag != nullptr && workspace != nullptr, SNGNN_EINVAL, "row_flag/workspace is NULL");
-    SN_REQUIRE(nrm != nullptr || filt == nullptr, SNGNN_EINVAL, "filter rows go with unit rows + norms");
-    SN_REQUIRE(filt == nullptr || filter_row_bytes(C) > 0, SNGNN_EINVAL,
-               "no filter rows for this C (sngnn_filter_row_bytes(C) == 0)");
-    SN_REQUIRE(((uintptr_t)filt % 16) == 0, SNGNN_EINVAL, "filt must be 16-byte aligned");
-    void *scratch = (char *)workspace + fwd_table_bytes(g->Ntot, C);
-    // (the caller decides whether filter rows exist - sngnn_filter_wanted - and passes them or NULL)
-    return forward_normalized(g, cfg, n, nrm, filt, C, top_k, thr, out, wsel, inv_norm, nullptr, nullptr, scratch,
-                              nullptr, (hipStream_t)stream, row_flag, row_want);
+    FwdCall c;
+    c.g = g; c.rows = n; c.prepared = true; c.nrm = nrm; c.filt = filt; c.by_rows = true; c.row_flag = row_flag;
+    c.row_want = row_want; c.C = C; c.top_k = top_k; c.thr = thr; c.out = out; c.wsel = wsel; c.inv_norm = inv_norm;
+    c.workspace = workspace; c.stream = stream;
+    return run_forward(c);
 }
 
 // (the forward side of the question: split rows must take the candidate finalize, whose winners set their bits)

@@ -468,7 +468,7 @@ template <int G> __device__ __forceinline__ unsigned long long fwd_group_bits(un
 // row-local edge index (the low word of a key is 0xFFFFFFFF - index, so its
 // upper 32 - lowbits bits are all ones and need no search).
 // ---------------------------------------------------------------------------
-constexpr int CAND_MAX_K = 32;   // split rows: chunk-local candidates are kept for k <= this
+// (CAND_MAX_K - split rows: chunk-local candidates are kept for k <= this: ws_layout.h, which sizes their records)
 
 // (wave_topk_keys_n: device_utils.h)
 __device__ __forceinline__ void wave_topk_keys(unsigned long long key0, unsigned long long key1,
@@ -2496,50 +2496,38 @@ int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hi
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int R>
+// S = float, or the half path (sngnn_agg_forward_half): rows h stored as S = __half / __hip_bfloat16, scored on the fly,
+// out stored as S.  The kernels are the fp32 ones with their row loads and output stores in S (device_utils.h: Row),
+// so every register holds what it holds in the fp32 forward of h.float(): same lanes, same order, same bits.
+template <int VEC, int G, int R, typename S = float>
 int launch_agg_fwd(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
 {
-    return launch_agg_fwd_impl<VEC, G, R, 0>(a, max_split_deg, ev, st);
+    return launch_agg_fwd_impl<VEC, G, R, 0, S>(a, max_split_deg, ev, st);
 }
 template <int VEC, int G, int R>
 int launch_agg_fwd_epi(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
 {
     return launch_agg_fwd_impl<VEC, G, R, 1>(a, max_split_deg, ev, st);
 }
-// the half path (sngnn_agg_forward_half): rows h stored as S = __half / __hip_bfloat16, scored on the fly, out
-// stored as S.  The kernels are the fp32 ones with their row loads and output stores in S (device_utils.h: Row),
-// so every register holds what it holds in the fp32 forward of h.float(): same lanes, same order, same bits.
-template <typename S> struct LaunchHalf {
-    template <int VEC, int G, int R>
-    static int run(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
-    {
-        return launch_agg_fwd_impl<VEC, G, R, 0, S>(a, max_split_deg, ev, st);
-    }
-};
 
-
-// one translation unit per VEC instantiates these
-int launch_agg_fwd_epi_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                          hipStream_t st);      // (the store epilogue: 16-byte rows only)
-int launch_agg_fwd_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                      hipStream_t st);
-int launch_agg_fwd_v2(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                      hipStream_t st);
-int launch_agg_fwd_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                      hipStream_t st);
-int launch_normalize_v1(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
-                        hipStream_t st);
-int launch_normalize_v2(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
-                        hipStream_t st);
-int launch_normalize_v4(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
-                        hipStream_t st);
+// Defined one per translation unit: storage type S (float, __half, __hip_bfloat16: agg_fwd[_f16|_bf16]_v*.hip) x VEC
+// values per lane (entry.h: SNGNN_LAUNCH_VEC).  The unit-row passes and the store epilogue exist for fp32 rows only,
+// the filter pass and the epilogue for 16-byte rows only (agg_fwd_v4.hip, agg_fwd_v4e.hip).
+template <typename S, int VEC>
+int launch_agg_fwd_vec(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+template <typename S, int VEC>
+int launch_normalize_vec(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
+                         hipStream_t st);
+int launch_agg_fwd_epi_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
 int launch_filter_v4(const RowCfg &cfg, const float *n, int64_t rows, int C, void *filt, hipStream_t st);
-// the half path, one translation unit per storage type and VEC (agg_fwd_f16_v*.hip, agg_fwd_bf16_v*.hip)
-int launch_agg_fwd_f16_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
-int launch_agg_fwd_f16_v2(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
-int launch_agg_fwd_f16_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
-int launch_agg_fwd_bf16_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
-int launch_agg_fwd_bf16_v2(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
-int launch_agg_fwd_bf16_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
 
 }  // namespace sngnn
+
+#define SNGNN_AGG_FWD_TU(S, VEC)                                                                                       \
+    template <>                                                                                                        \
+    int sngnn::launch_agg_fwd_vec<S, VEC>(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,      \
+                                          hipStream_t st)                                                              \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_agg_fwd, VEC, S, cfg, a, max_split_deg, ev, st)                                      \
+    }
+

@@ -1,16 +1,13 @@
 // Instantiates the fused aggregation forward for rows read 1 float(s) per lane.
 #include "agg_fwd_impl.h"
 
+SNGNN_AGG_FWD_TU(float, 1)
+
 namespace sngnn {
 
-int launch_agg_fwd_v1(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                      hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(launch_agg_fwd, 1, cfg, a, max_split_deg, ev, st)
-}
-
-int launch_normalize_v1(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm,
-                        void *filt, hipStream_t st)
+template <>
+int launch_normalize_vec<float, 1>(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
+                                   hipStream_t st)
 {
     SNGNN_DISPATCH_GR(launch_normalize_rows, 1, cfg, h, rows, C, n, nrm, filt, st)
 }

@@ -1,16 +1,13 @@
 // Instantiates the fused aggregation forward for rows read 4 float(s) per lane.
 #include "agg_fwd_impl.h"
 
+SNGNN_AGG_FWD_TU(float, 4)
+
 namespace sngnn {
 
-int launch_agg_fwd_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,
-                      hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(launch_agg_fwd, 4, cfg, a, max_split_deg, ev, st)
-}
-
-int launch_normalize_v4(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm,
-                        void *filt, hipStream_t st)
+template <>
+int launch_normalize_vec<float, 4>(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
+                                   hipStream_t st)
 {
     SNGNN_DISPATCH_GR(launch_normalize_rows, 4, cfg, h, rows, C, n, nrm, filt, st)
 }

@@ -1,17 +1,5 @@
 // Instantiates the half path's cosine-attention kernels for fp16 rows read 2 value(s) per lane
-// (attn_impl.h: LaunchAttnHalf).
+// (attn_impl.h: SNGNN_ATTN_TU).
 #include "attn_impl.h"
 
-namespace sngnn {
-
-int launch_attn_fwd_f16_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(LaunchAttnHalf<__half>::fwd, 2, cfg, a, st)
-}
-
-int launch_attn_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(LaunchAttnHalf<__half>::bwd, 2, cfg, a, st)
-}
-
-}  // namespace sngnn
+SNGNN_ATTN_TU(__half, 2)

@@ -446,35 +446,20 @@ template <int VEC, int G, int R, typename S = float> int launch_attn_bwd(const B
     return SNGNN_OK;
 }
 
-int launch_attn_fwd_v1(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_bwd_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-// the half path (sngnn_attn_forward_half / sngnn_attn_backward_half: h, out, gout and grad_h stored as S), one
-// translation unit per storage type and VEC (attn_f16_v*.hip, attn_bf16_v*.hip)
-template <typename S> struct LaunchAttnHalf {
-    template <int VEC, int G, int R> static int fwd(const AttnArgs &a, hipStream_t st)
-    {
-        return launch_attn_fwd<VEC, G, R, S>(a, st);
-    }
-    template <int VEC, int G, int R> static int bwd(const BwdArgs &a, hipStream_t st)
-    {
-        return launch_attn_bwd<VEC, G, R, S>(a, st);
-    }
-};
-int launch_attn_fwd_f16_v1(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_f16_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_f16_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_bf16_v1(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_bf16_v2(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_fwd_bf16_v4(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
-int launch_attn_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
-int launch_attn_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
+// defined one per translation unit: storage type S (float, or the half path - sngnn_attn_forward_half /
+// sngnn_attn_backward_half: h, out, gout and grad_h stored as S) x VEC values per lane (attn[_f16|_bf16]_v*.hip)
+template <typename S, int VEC> int launch_attn_fwd_vec(const RowCfg &cfg, const AttnArgs &a, hipStream_t st);
+template <typename S, int VEC> int launch_attn_bwd_vec(const RowCfg &cfg, const BwdArgs &a, hipStream_t st);
 
 }  // namespace sngnn
+
+#define SNGNN_ATTN_TU(S, VEC)                                                                                          \
+    template <> int sngnn::launch_attn_fwd_vec<S, VEC>(const RowCfg &cfg, const AttnArgs &a, hipStream_t st)           \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_attn_fwd, VEC, S, cfg, a, st)                                                        \
+    }                                                                                                                  \
+    template <> int sngnn::launch_attn_bwd_vec<S, VEC>(const RowCfg &cfg, const BwdArgs &a, hipStream_t st)            \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_attn_bwd, VEC, S, cfg, a, st)                                                        \
+    }
+

@@ -4,9 +4,11 @@
 #include <stdint.h>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sngnn_hip.h"
+#include "ws_layout.h"   // filter_row_bytes, CAND_MAX_K, the workspace layouts
 
 namespace sngnn {
 
@@ -55,7 +57,7 @@ inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 //   VEC floats per lane per step, G lanes per group, R steps  (C <= VEC*G*R).
 struct RowCfg { int vec, g, r; };
 // (the forward, backward, attention and adjacency kernels are instantiated for the layouts
-// this function can return: SNGNN_DISPATCH_GR below)
+// this function can return: dispatch_gr below)
 inline bool row_cfg(int C, RowCfg &cfg)
 {
     if (C < 1 || C > SNGNN_MAX_CHANNELS) return false;
@@ -71,37 +73,30 @@ inline bool row_cfg(int C, RowCfg &cfg)
     return true;
 }
 
-// bytes of one fp16 filter row (agg_fwd_filter.h): whole 128-byte lines; 0 = no filter for this C
-// (it pays when a unit row is longer than one line and the rows are 16-byte vectors)
-inline int64_t filter_row_bytes(int C)
-{
-    if (C % 4 != 0 || C <= 32 || C > SNGNN_MAX_CHANNELS) return 0;
-    int64_t b = 128;                 // 2 bytes x (4 G R) channels of the row layout: 64, 128, 256 or 512
-    while (b < 2 * (int64_t)C) b <<= 1;
-    return b;
-}
-
-// bytes of the forward's unit-row table + norms + filter rows in front of its scratch inside
-// the workspace (256-byte aligned regions)
-inline int64_t fwd_table_bytes(int64_t Ntot, int C)
-{
-    return (Ntot * (int64_t)C * 4 + 255) / 256 * 256 + (Ntot * 4 + 255) / 256 * 256 +
-           (Ntot * filter_row_bytes(C) + 255) / 256 * 256;
-}
-
 }  // namespace sngnn
 
-#define SNGNN_DISPATCH_GR(FN, VEC, cfg, ...)                                   \
-    switch ((cfg).g * 100 + (cfg).r) {                                         \
-    case 801: return FN<VEC, 8, 1>(__VA_ARGS__);                               \
-    case 1601: return FN<VEC, 16, 1>(__VA_ARGS__);                             \
-    case 3201: return FN<VEC, 32, 1>(__VA_ARGS__);                             \
-    case 6401: return FN<VEC, 64, 1>(__VA_ARGS__);                             \
-    case 6402: return FN<VEC, 64, 2>(__VA_ARGS__);                             \
-    case 6404: return FN<VEC, 64, 4>(__VA_ARGS__);                             \
-    case 6408: return FN<VEC, 64, 8>(__VA_ARGS__);                             \
-    default: sngnn::set_error("unsupported channel layout"); return SNGNN_EINVAL; \
+namespace sngnn {
+// f(std::integral_constant<int, G>, std::integral_constant<int, R>) for the lane layout of cfg
+template <typename F> int dispatch_gr(const RowCfg &cfg, F &&f)
+{
+    using std::integral_constant;
+    switch (cfg.g * 100 + cfg.r) {
+    case 801: return f(integral_constant<int, 8>{}, integral_constant<int, 1>{});
+    case 1601: return f(integral_constant<int, 16>{}, integral_constant<int, 1>{});
+    case 3201: return f(integral_constant<int, 32>{}, integral_constant<int, 1>{});
+    case 6401: return f(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    case 6402: return f(integral_constant<int, 64>{}, integral_constant<int, 2>{});
+    case 6404: return f(integral_constant<int, 64>{}, integral_constant<int, 4>{});
+    case 6408: return f(integral_constant<int, 64>{}, integral_constant<int, 8>{});
+    default: set_error("unsupported channel layout"); return SNGNN_EINVAL;
     }
+}
+}  // namespace sngnn
+// return FN<VEC, G, R>(...), and with a storage type S: return FN<VEC, G, R, S>(...)
+#define SNGNN_DISPATCH_GR(FN, VEC, cfg, ...)                                                                           \
+    return sngnn::dispatch_gr(cfg, [&](auto g, auto r) { return FN<VEC, decltype(g)::value, decltype(r)::value>(__VA_ARGS__); });
+#define SNGNN_DISPATCH_GRS(FN, VEC, S, cfg, ...)                                                                       \
+    return sngnn::dispatch_gr(cfg, [&](auto g, auto r) { return FN<VEC, decltype(g)::value, decltype(r)::value, S>(__VA_ARGS__); });
 
 // The graph object behind the opaque handle.
 struct sngnn_graph {

@@ -27,6 +27,7 @@
 //   grad_att_src[h,c] = sum_j grad_a_src[j,h] xp[j,h,c] (grad_att_dst alike): per-workgroup partials in double,
 //                        added in a fixed order by a reducer launch
 #include "device_utils.h"
+#include "entry.h"
 
 namespace sngnn {
 
@@ -404,15 +405,7 @@ static void gat_side(const sngnn_graph_t *g, bool transpose, GatArgs &a)
 {
     a.N = (int)g->N;
     a.csc_pos = g->csc_pos;
-    if (!transpose) {
-        a.ptr = g->rowptr; a.idx = g->col; a.perm = g->rperm;
-        a.n_split = g->n_split; a.n_med_end = g->rows_gt(SMALL_T); a.n_tasks = g->n_tasks;
-        a.task_slot = g->task_slot; a.task_chunk = g->task_chunk; a.split_task0 = g->split_task0;
-    } else {
-        a.ptr = g->cscptr; a.idx = g->csc_dst; a.perm = g->sperm;
-        a.n_split = g->n_ssplit; a.n_med_end = g->srcs_gt(SMALL_T); a.n_tasks = g->n_stasks;
-        a.task_slot = g->stask_slot; a.task_chunk = g->stask_chunk; a.split_task0 = g->ssplit_task0;
-    }
+    bind_side(g, transpose, a);
     a.nbA = ceil_div(a.n_tasks, WAVES);
     a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
 }
@@ -453,17 +446,11 @@ template <int VEC, int G, int R> int launch_gat_bwd_s(const GatArgs &a, hipStrea
 #define GAT_DISPATCH(NAME, FN)                                                                                         \
     static int NAME(const RowCfg &cfg, const GatArgs &a, hipStream_t st)                                               \
     {                                                                                                                  \
-        switch (cfg.vec) {                                                                                             \
-        case 1: SNGNN_DISPATCH_GR(FN, 1, cfg, a, st)                                                                   \
-        case 2: SNGNN_DISPATCH_GR(FN, 2, cfg, a, st)                                                                   \
-        default: SNGNN_DISPATCH_GR(FN, 4, cfg, a, st)                                                                  \
-        }                                                                                                              \
+        return dispatch_vec(cfg, [&](auto vec) { SNGNN_DISPATCH_GR(FN, decltype(vec)::value, cfg, a, st) });          \
     }
 GAT_DISPATCH(dispatch_gat_fwd, launch_gat_fwd)
 GAT_DISPATCH(dispatch_gat_bwd_t, launch_gat_bwd_t)
 GAT_DISPATCH(dispatch_gat_bwd_s, launch_gat_bwd_s)
-
-static int64_t gat_up256(int64_t v) { return (v + 255) / 256 * 256; }
 
 static int gat_att_npb(int64_t N) { return (int)std::max<int64_t>(8, (N + GAT_ATT_BLOCKS - 1) / GAT_ATT_BLOCKS); }
 
@@ -475,25 +462,13 @@ static GatLayout gat_layout(const sngnn_graph_t *g, int H, int C)
 {
     GatLayout L;
     const int64_t tasks = std::max(g->n_tasks, g->n_stasks);
-    L.tml = gat_up256(tasks * H * C * 4);
-    L.rec = L.tml + gat_up256(tasks * H * 2 * 4);
-    L.gasrc = L.rec + gat_up256(g->Ep * H * 2 * 4);
-    L.gadst = L.gasrc + gat_up256(g->N * H * 4);
-    L.att = L.gadst + gat_up256(g->N * H * 4);
-    L.total = L.att + gat_up256((int64_t)ceil_div(std::max<int64_t>(g->N, 1), gat_att_npb(g->N)) * 2 * H * C * 8);
+    L.tml = up256(tasks * H * C * 4);
+    L.rec = L.tml + up256(tasks * H * 2 * 4);
+    L.gasrc = L.rec + up256(g->Ep * H * 2 * 4);
+    L.gadst = L.gasrc + up256(g->N * H * 4);
+    L.att = L.gadst + up256(g->N * H * 4);
+    L.total = L.att + up256((int64_t)ceil_div(std::max<int64_t>(g->N, 1), gat_att_npb(g->N)) * 2 * H * C * 8);
     return L;
-}
-
-static bool gat_graph_ok(const sngnn_graph_t *g)
-{
-    return g->add_loops == 1 && g->remove_loops == SNGNN_LOOPS_REPLACE && g->N == g->Ntot && g->row_off == 0;
-}
-
-static bool gat_aligned(std::initializer_list<const void *> ps)
-{
-    uintptr_t a = 0;
-    for (const void *p : ps) a |= (uintptr_t)p;
-    return a % 16 == 0;
 }
 
 }  // namespace sngnn
@@ -509,7 +484,7 @@ using namespace sngnn;
 
 #define GAT_GRAPH(g)                                                                                                   \
     SN_REQUIRE((g) != nullptr, SNGNN_EINVAL, "graph is NULL");                                                         \
-    SN_REQUIRE(gat_graph_ok(g), SNGNN_EINVAL,                                                                          \
+    SN_REQUIRE(whole_graph_with_loops(g), SNGNN_EINVAL,                                                                \
                "the graph attention needs an unpartitioned graph built with add_loops = 1, remove_loops = "           \
                "SNGNN_LOOPS_REPLACE (GATConv's edge list)")
 
@@ -540,7 +515,7 @@ extern "C" int sngnn_gat_forward(const sngnn_graph_t *g, const float *xp, const 
     GAT_SHAPE(H, C);
     if (g->N == 0) return SNGNN_OK;
     SN_REQUIRE(xp && a_src && a_dst && out && ml && workspace, SNGNN_EINVAL, "NULL argument");
-    SN_REQUIRE(gat_aligned({xp, out, workspace}), SNGNN_EINVAL, "rows must be aligned to 16 bytes");
+    SN_REQUIRE(rows_aligned(16, {xp, out, workspace}), SNGNN_EINVAL, "rows must be aligned to 16 bytes");
     const GatLayout L = gat_layout(g, H, C);
     GatArgs a = {};
     gat_side(g, false, a);
@@ -562,7 +537,7 @@ extern "C" int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out,
     if (g->N == 0) return SNGNN_OK;
     SN_REQUIRE(grad_out && xp && out && a_src && a_dst && ml && att_src && att_dst && workspace, SNGNN_EINVAL,
                "NULL argument");
-    SN_REQUIRE(gat_aligned({grad_out, xp, out, att_src, att_dst, grad_xp, workspace}), SNGNN_EINVAL,
+    SN_REQUIRE(rows_aligned(16, {grad_out, xp, out, att_src, att_dst, grad_xp, workspace}), SNGNN_EINVAL,
                "rows must be aligned to 16 bytes");
     hipStream_t st = (hipStream_t)stream;
     const GatLayout L = gat_layout(g, H, C);

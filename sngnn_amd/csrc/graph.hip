@@ -591,19 +591,8 @@ int64_t sngnn_graph_num_fused_nodes(const sngnn_graph_t *g) { return g ? g->n_fu
 int64_t sngnn_graph_workspace_bytes(const sngnn_graph_t *g, int C)
 {
     if (!g || C < 1) return -1;
-    // forward: unit rows | norms | scores of split rows | one partial row per split task |
-    //          CAND_MAX_K candidate keys and source ids per task | one done word per task (the finalize role: agg_fwd_impl.h)
-    int64_t fwd = sngnn::fwd_table_bytes(g->Ntot, C) +
-                  (g->split_edges + 3) / 4 * 4 * 4 + ((int64_t)g->n_tasks * C + 3) / 4 * 4 * 4 +
-                  (int64_t)g->n_tasks * 32 * 8 + (int64_t)g->n_tasks * 32 * 4 + (int64_t)g->n_tasks * 8;
-    // backward: {w, ds} record per edge | dnT per node | partT per split task | partS (2 rows) per
-    //           split-source task
-    //           (attention mode: 2 rows + 4 scalars) | partS (2 rows) per split-source task
-    int64_t bwd = (2 * g->Ep + 3) / 4 * 4 * 4 + g->N * (int64_t)C * 4 +
-                  (int64_t)g->n_tasks * (2 * C + 4) * 4 + (int64_t)g->n_stasks * C * 4 * 2 +
-                  (g->N + 3) / 4 * 4 * 4;            // (attention mode: dot_i per target, BwdArgs::rec_dot)
-    int64_t b = std::max(fwd, bwd);
-    return (b + 255) / 256 * 256;
+    // the rounded maximum of the forward's and the backward's layouts (ws_layout.h defines every region)
+    return sngnn::graph_workspace_bytes(g->N, g->Ntot, g->Ep, g->n_tasks, g->n_stasks, g->split_edges, C);
 }
 
 static const void *graph_array(const sngnn_graph_t *g, int which, int64_t *n)

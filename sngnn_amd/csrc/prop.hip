@@ -14,6 +14,7 @@
 //                  one reducer launch adds them in a fixed order                             (CSC side)
 //   APPNP          x_{k+1} = alpha h + (1 - alpha) A^ x_k; its backward is the same recurrence on A^T
 #include "device_utils.h"
+#include "entry.h"
 
 namespace sngnn {
 
@@ -260,26 +261,14 @@ template <int VEC, int G, int R> int launch_prop(const PropArgs &a0, hipStream_t
 
 static int dispatch_prop(const RowCfg &cfg, const PropArgs &a, hipStream_t st)
 {
-    switch (cfg.vec) {
-    case 1: SNGNN_DISPATCH_GR(launch_prop, 1, cfg, a, st)
-    case 2: SNGNN_DISPATCH_GR(launch_prop, 2, cfg, a, st)
-    default: SNGNN_DISPATCH_GR(launch_prop, 4, cfg, a, st)
-    }
+    return dispatch_vec(cfg, [&](auto vec) { SNGNN_DISPATCH_GR(launch_prop, decltype(vec)::value, cfg, a, st) });
 }
 
 // the structure a hop walks: the in-edges (CSR by target) or, for A^T, the out-edges (CSC by source)
 static void prop_side(const sngnn_graph_t *g, bool transpose, PropArgs &a)
 {
     a.N = (int)g->N;
-    if (!transpose) {
-        a.ptr = g->rowptr; a.idx = g->col; a.perm = g->rperm;
-        a.n_split = g->n_split; a.n_med_end = g->rows_gt(SMALL_T); a.n_tasks = g->n_tasks;
-        a.task_slot = g->task_slot; a.task_chunk = g->task_chunk; a.split_task0 = g->split_task0;
-    } else {
-        a.ptr = g->cscptr; a.idx = g->csc_dst; a.perm = g->sperm;
-        a.n_split = g->n_ssplit; a.n_med_end = g->srcs_gt(SMALL_T); a.n_tasks = g->n_stasks;
-        a.task_slot = g->stask_slot; a.task_chunk = g->stask_chunk; a.split_task0 = g->ssplit_task0;
-    }
+    bind_side(g, transpose, a);
     a.nbA = a.nbB = 0;
 }
 
@@ -291,8 +280,6 @@ static int prop_parts(const sngnn_graph_t *g, bool transpose, const RowCfg &cfg)
     return ceil_div(a.n_med_end - a.n_split, WAVES) + ceil_div(a.N - a.n_med_end, (int64_t)WAVES * (64 / cfg.g)) +
            a.n_split;
 }
-
-static int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 
 struct PropLayout { int64_t u1, partial, dots, total, stride; };
 
@@ -310,35 +297,23 @@ static PropLayout prop_layout(const sngnn_graph_t *g, int C, int K, const RowCfg
 
 static int prop_init_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(PROP_INIT_BLOCKS, (n + 255) / 256)); }
 
-static bool prop_graph_ok(const sngnn_graph_t *g)
-{
-    return g->add_loops == 1 && g->remove_loops == SNGNN_LOOPS_REPLACE && g->N == g->Ntot && g->row_off == 0;
-}
-
 }  // namespace sngnn
 
 using namespace sngnn;
 
 #define PROP_COMMON(g, C, K)                                                                                           \
     SN_REQUIRE((g) != nullptr, SNGNN_EINVAL, "graph is NULL");                                                         \
-    SN_REQUIRE(prop_graph_ok(g), SNGNN_EINVAL,                                                                         \
+    SN_REQUIRE(whole_graph_with_loops(g), SNGNN_EINVAL,                                                                \
                "the propagation needs an unpartitioned graph built with add_loops = 1, remove_loops = "              \
                "SNGNN_LOOPS_REPLACE (gcn_norm's edge list)");                                                          \
     SN_REQUIRE((K) >= 1, SNGNN_EINVAL, "K must be at least 1");                                                        \
     RowCfg cfg;                                                                                                        \
     SN_REQUIRE(row_cfg((C), cfg), SNGNN_EINVAL, "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]")
 
-static bool prop_aligned(const RowCfg &cfg, std::initializer_list<const void *> ps)
-{
-    uintptr_t a = 0;
-    for (const void *p : ps) a |= (uintptr_t)p;
-    return a % ((uintptr_t)cfg.vec * 4) == 0;
-}
-
 extern "C" int sngnn_prop_dinv(const sngnn_graph_t *g, float *dinv, void *stream)
 {
     SN_REQUIRE(g != nullptr, SNGNN_EINVAL, "graph is NULL");
-    SN_REQUIRE(prop_graph_ok(g), SNGNN_EINVAL,
+    SN_REQUIRE(whole_graph_with_loops(g), SNGNN_EINVAL,
                "the propagation needs an unpartitioned graph built with add_loops = 1, remove_loops = "
                "SNGNN_LOOPS_REPLACE (gcn_norm's edge list)");
     if (g->N == 0) return SNGNN_OK;
@@ -361,7 +336,7 @@ extern "C" int sngnn_prop_gpr_forward(const sngnn_graph_t *g, const float *x, co
     PROP_COMMON(g, C, K);
     if (g->N == 0) return SNGNN_OK;
     SN_REQUIRE(x && gamma && dinv && out && workspace, SNGNN_EINVAL, "NULL argument");
-    SN_REQUIRE(prop_aligned(cfg, {x, out}), SNGNN_EINVAL, "rows must be aligned to the row vector width");
+    SN_REQUIRE(rows_aligned((uintptr_t)cfg.vec * 4, {x, out}), SNGNN_EINVAL, "rows must be aligned to the row vector width");
     hipStream_t st = (hipStream_t)stream;
     const PropLayout L = prop_layout(g, C, K, cfg);
     float *u[2] = {(float *)workspace, (float *)((char *)workspace + L.u1)};
@@ -396,7 +371,8 @@ extern "C" int sngnn_prop_gpr_backward(const sngnn_graph_t *g, const float *grad
     }
     SN_REQUIRE(grad_out && gamma && dinv && workspace, SNGNN_EINVAL, "NULL argument");
     SN_REQUIRE(!grad_gamma || x, SNGNN_EINVAL, "grad_gamma needs x");
-    SN_REQUIRE(prop_aligned(cfg, {grad_out, x, grad_x}), SNGNN_EINVAL, "rows must be aligned to the row vector width");
+    SN_REQUIRE(rows_aligned((uintptr_t)cfg.vec * 4, {grad_out, x, grad_x}), SNGNN_EINVAL,
+               "rows must be aligned to the row vector width");
     const PropLayout L = prop_layout(g, C, K, cfg);
     float *u[2] = {(float *)workspace, (float *)((char *)workspace + L.u1)};
     double *dots = (double *)((char *)workspace + L.dots);
@@ -430,7 +406,7 @@ extern "C" int sngnn_prop_appnp(const sngnn_graph_t *g, const float *h, const fl
     PROP_COMMON(g, C, K);
     if (g->N == 0) return SNGNN_OK;
     SN_REQUIRE(h && coef && dinv && out && workspace, SNGNN_EINVAL, "NULL argument");
-    SN_REQUIRE(prop_aligned(cfg, {h, out}), SNGNN_EINVAL, "rows must be aligned to the row vector width");
+    SN_REQUIRE(rows_aligned((uintptr_t)cfg.vec * 4, {h, out}), SNGNN_EINVAL, "rows must be aligned to the row vector width");
     hipStream_t st = (hipStream_t)stream;
     const PropLayout L = prop_layout(g, C, K, cfg);
     float *u[2] = {(float *)workspace, (float *)((char *)workspace + L.u1)};

@@ -19,6 +19,7 @@
 //                               the grid and reduction tree of sngnn_blend_backward
 // Every sum is fixed-order: no float atomics.  Nothing here blocks the host.
 #include "agg_fwd_impl.h"
+#include "entry.h"
 #include "head_row.h"
 
 namespace sngnn {
@@ -116,11 +117,9 @@ int launch_rep_unpack(const float *hs, const float *bias, int64_t N, int NR, int
 int dispatch_rep_unpack(const RowCfg &cfg, const float *hs, const float *bias, int64_t N, int NR, int C, float *h,
                         float *n, float *nrm, void *filt, hipStream_t st)
 {
-    switch (cfg.vec) {
-    case 1: SNGNN_DISPATCH_GR(launch_rep_unpack, 1, cfg, hs, bias, N, NR, C, h, n, nrm, filt, st)
-    case 2: SNGNN_DISPATCH_GR(launch_rep_unpack, 2, cfg, hs, bias, N, NR, C, h, n, nrm, filt, st)
-    default: SNGNN_DISPATCH_GR(launch_rep_unpack, 4, cfg, hs, bias, N, NR, C, h, n, nrm, filt, st)
-    }
+    return dispatch_vec(cfg, [&](auto vec) {
+        SNGNN_DISPATCH_GR(launch_rep_unpack, decltype(vec)::value, cfg, hs, bias, N, NR, C, h, n, nrm, filt, st)
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -539,11 +538,7 @@ extern "C" int sngnn_replica_unpack(const float *hs, const float *bias, int64_t 
     SN_REQUIRE((n == nullptr) == (nrm == nullptr), SNGNN_EINVAL, "n and nrm go together");
     SN_REQUIRE(filt == nullptr || n != nullptr, SNGNN_EINVAL, "filter rows need the unit rows");
     RowCfg cfg;
-    SN_REQUIRE(row_cfg(C, cfg), SNGNN_EINVAL, "C must be in [1, " + std::to_string(SNGNN_MAX_CHANNELS) + "]");
-    const uintptr_t al = (uintptr_t)cfg.vec * 4;
-    SN_REQUIRE((uintptr_t)hs % al == 0 && (uintptr_t)h % al == 0 && (n == nullptr || (uintptr_t)n % al == 0) &&
-                   (bias == nullptr || (uintptr_t)bias % al == 0),
-               SNGNN_EINVAL, "hs/h/n/bias must be aligned to the row vector width");
+    if (int rc = check_rows(C, 0, {hs, h, n, bias}, cfg)) return rc;
     SN_REQUIRE(filt == nullptr || filter_row_bytes(C) > 0, SNGNN_EINVAL,
                "no filter rows for this C (sngnn_filter_row_bytes(C) == 0)");
     SN_REQUIRE(((uintptr_t)filt % 16) == 0, SNGNN_EINVAL, "filt must be 16-byte aligned");

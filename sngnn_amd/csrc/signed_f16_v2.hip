@@ -1,17 +1,5 @@
 // Instantiates the half path's signed cosine-attention kernels for fp16 rows read 2 value(s) per lane
-// (signed_impl.h: LaunchSignedHalf).
+// (signed_impl.h: SNGNN_SIGNED_TU).
 #include "signed_impl.h"
 
-namespace sngnn {
-
-int launch_signed_fwd_f16_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(LaunchSignedHalf<__half>::fwd, 2, cfg, a, st)
-}
-
-int launch_signed_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st)
-{
-    SNGNN_DISPATCH_GR(LaunchSignedHalf<__half>::bwd, 2, cfg, a, x, st)
-}
-
-}  // namespace sngnn
+SNGNN_SIGNED_TU(__half, 2)

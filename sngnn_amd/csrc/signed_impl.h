@@ -359,35 +359,23 @@ template <int VEC, int G, int R, typename S = float> int launch_signed_bwd(const
     return SNGNN_OK;
 }
 
-int launch_signed_fwd_v1(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_bwd_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-// the half path (sngnn_signed_forward_half / sngnn_signed_backward_half: Wh, out, gout and grad_wh stored as S), one
-// translation unit per storage type and VEC (signed_f16_v*.hip, signed_bf16_v*.hip)
-template <typename S> struct LaunchSignedHalf {
-    template <int VEC, int G, int R> static int fwd(const SignedArgs &a, hipStream_t st)
-    {
-        return launch_signed_fwd<VEC, G, R, S>(a, st);
-    }
-    template <int VEC, int G, int R> static int bwd(const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st)
-    {
-        return launch_signed_bwd<VEC, G, R, S>(a, x, st);
-    }
-};
-int launch_signed_fwd_f16_v1(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_f16_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_f16_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_bf16_v1(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_bf16_v2(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_fwd_bf16_v4(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
-int launch_signed_bwd_f16_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_f16_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_f16_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_bf16_v1(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_bf16_v2(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
-int launch_signed_bwd_bf16_v4(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
+// defined one per translation unit: storage type S (float, or the half path - sngnn_signed_forward_half /
+// sngnn_signed_backward_half: Wh, out, gout and grad_wh stored as S) x VEC values per lane (signed[_f16|_bf16]_v*.hip)
+template <typename S, int VEC> int launch_signed_fwd_vec(const RowCfg &cfg, const SignedArgs &a, hipStream_t st);
+template <typename S, int VEC>
+int launch_signed_bwd_vec(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x, hipStream_t st);
 
 }  // namespace sngnn
+
+#define SNGNN_SIGNED_TU(S, VEC)                                                                                        \
+    template <> int sngnn::launch_signed_fwd_vec<S, VEC>(const RowCfg &cfg, const SignedArgs &a, hipStream_t st)       \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_signed_fwd, VEC, S, cfg, a, st)                                                      \
+    }                                                                                                                  \
+    template <>                                                                                                        \
+    int sngnn::launch_signed_bwd_vec<S, VEC>(const RowCfg &cfg, const BwdArgs &a, const SignedBwdExtra &x,             \
+                                             hipStream_t st)                                                           \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GRS(launch_signed_bwd, VEC, S, cfg, a, x, st)                                                   \
+    }
+
