@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("SNGNN_LIB_PATH") or os.path.join(_HERE, "libsngnn_hip
 OK, EINVAL, ERANGE, EHIP, ENOMEM = 0, -1, -2, -3, -4
 DTYPE_F16, DTYPE_BF16 = 1, 2          # SNGNN_DTYPE_*: storage types of the half path's rows
 UNSELECTED = -4.0
+LOOPS_REPLACE = 2      # SNGNN_LOOPS_REPLACE: drop the original loops, then append one per node
 MAX_CHANNELS = 512
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float

@@ -226,7 +226,7 @@ def _aggregate(h: torch.Tensor, graph, shard, top_k, thr: float, table=None, uni
     rank's in-edges reference are exchanged first (RCCL) - in the halo form overlapped with the
     aggregation of the rows that need none of them (sngnn_amd/dist.py:halo_aggregate)."""
     if shard is None:
-        return ops.aggregate(h, graph, top_k, thr, unit)
+        return ops.aggregate(h, graph, top_k, thr, unit=unit)
     if shard.plan is not None:
         return sn_dist.halo_aggregate(h, shard.plan, graph, top_k, thr, table)
     return ops.aggregate(shard.table(h), graph, top_k, thr)
@@ -256,6 +256,17 @@ def half_width(c: int) -> int:
     return 4 * g * rr
 
 
+def _half_lin(x, lin, fold=None) -> torch.Tensor:
+    """``lin(x)`` of the half path: torch's F.linear, the rows padded to ``half_width`` (see HALF_PAD's note)."""
+    c = lin.out_features
+    weight, bias = (lin.weight, lin.bias) if fold is None else fold.apply(lin)
+    cp = half_width(c)
+    if cp != c:
+        weight = F.pad(weight, (0, 0, 0, cp - c))
+        bias = None if bias is None else F.pad(bias, (0, cp - c))
+    return F.linear(x, weight, bias)
+
+
 def _half_conv(x, edge_index, lin, add_loops, remove_loops, top_k, thr, epilogue=None, head=None, fold=None):
     """(mean aggregation of lin(x) in x's half dtype, graph) - see HALF_PAD's note."""
     if epilogue is not None:
@@ -263,14 +274,44 @@ def _half_conv(x, edge_index, lin, add_loops, remove_loops, top_k, thr, epilogue
     if head is not None:
         head.applied = False
     graph, _ = _graph_for(x, edge_index, add_loops, remove_loops)       # (a partition refuses half features)
-    c = lin.out_features
-    weight, bias = (lin.weight, lin.bias) if fold is None else fold.apply(lin)
-    cp = half_width(c)
-    if cp != c:
-        weight = F.pad(weight, (0, 0, 0, cp - c))
-        bias = None if bias is None else F.pad(bias, (0, cp - c))
-    h = F.linear(x, weight, bias)
-    return _true_width(ops.aggregate(h, graph, top_k, thr), c), graph
+    return _true_width(ops.aggregate(_half_lin(x, lin, fold), graph, top_k, thr), lin.out_features), graph
+
+
+def _add_bias(out: torch.Tensor, bias, epilogue=None) -> torch.Tensor:
+    """The conv's bias behind a store that did not add it: added here, or left in ``epilogue.bias`` where the
+    epilogue's owner asked for it (``defer_bias`` - models._Stack: the fused batch norm adds it)."""
+    if bias is None:
+        return out
+    if epilogue is not None and epilogue.defer_bias:
+        epilogue.bias = bias
+        return out
+    return out + bias
+
+
+def _sn_lin(layer, x, edge_index, remove_loops: bool, top_k, thr: float, act_in, fold):
+    """The first half of an SN layer's fp32 forward: the graph, ``h = lin(x)`` and - with a selection (``top_k`` not
+    None) - the unit rows ``lin`` leaves for it and the layer's filter hint, probed when due.  Returns
+    (graph, shard, unit, h, true width, the rank's feature table or None)."""
+    graph, shard = _graph_for(x, edge_index, True, remove_loops)
+    unit = None          # (no selection: the aggregation scores straight from h - no unit rows wanted from lin)
+    if top_k is not None:
+        hint = layer._filter_hint()
+        hint.poll()
+        unit = _unit_for(layer.lin, graph, top_k, thr, hint)
+    h, c, table = _lin_aligned(x, layer.lin, shard, unit, act_in, fold)
+    if unit is not None and shard is None and (unit.want_filter or unit.no_filter) and hint.due():
+        hint.probe(h.detach(), edge_index, thr, ops.filter_wanted(graph, h.size(1), top_k, 0.0))
+    return graph, shard, unit, h, c, table
+
+
+def _sn_aggregate(h, c, table, graph, shard, unit, top_k, thr: float, bias, epilogue, head) -> torch.Tensor:
+    """The second half: the aggregation of ``h`` at its true width ``c`` with the layer's ``bias`` - in the head's or
+    the hidden epilogue's fused store where the shape takes one (``.applied`` says so), added behind it otherwise."""
+    if _fuse_head(head, graph, h, c, shard, top_k):
+        return ops.aggregate(h, graph, top_k, thr, unit=unit, bias=bias, head=head)
+    if _fuse_epilogue(epilogue, h, c, shard):
+        return ops.aggregate(h, graph, top_k, thr, unit=unit, epilogue=epilogue, bias=bias)
+    return _add_bias(_true_width(_aggregate(h, graph, shard, top_k, thr, table, unit), c), bias, epilogue)
 
 
 class SNConv(nn.Module):
@@ -300,22 +341,10 @@ class SNConv(nn.Module):
         layer): the classification head inside the aggregation's launches (ops.HeadEpilogue; ``head.applied``).
         ``fold``: a ``LinFold`` - an evaluation-mode batch norm in front of this layer, folded into ``lin``."""
         if x.dtype in ops.HALF_DTYPES:
-            out, _ = _half_conv(x, edge_index, self.lin, True, False, None, 0.0, epilogue, head, fold)
-            return out if self.bias is None else out + self.bias
-        graph, shard = _graph_for(x, edge_index, True, False)
-        # (no selection: the aggregation scores straight from h - no unit rows wanted from lin)
-        h, c, table = _lin_aligned(x, self.lin, shard, None, act_in, fold)
-        if _fuse_head(head, graph, h, c, shard, None):
-            return ops.aggregate(h, graph, None, 0.0, None, None, self.bias, head)
-        if _fuse_epilogue(epilogue, h, c, shard):
-            return ops.aggregate(h, graph, None, 0.0, None, epilogue, self.bias)
-        out = _true_width(_aggregate(h, graph, shard, None, 0.0, table), c)
-        if self.bias is not None:
-            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
-                epilogue.bias = self.bias
-            else:
-                out = out + self.bias
-        return out
+            out, _ = _half_conv(x, edge_index, self.lin, True, False, None, 0.0, epilogue=epilogue, head=head, fold=fold)
+            return _add_bias(out, self.bias)
+        graph, shard, unit, h, c, table = _sn_lin(self, x, edge_index, False, None, 0.0, act_in, fold)
+        return _sn_aggregate(h, c, table, graph, shard, unit, None, 0.0, self.bias, epilogue, head)
 
 
 class AGNNConv(nn.Module):
@@ -339,12 +368,7 @@ class AGNNConv(nn.Module):
             # the half path (see HALF_PAD's note): ``lin`` is torch's F.linear, the attention the library's half
             # kernels - the fp32 operator on h.float(), only its output rounded to the type
             graph, _ = _graph_for(x, edge_index, True, LOOPS_REPLACE)       # (a partition refuses half features)
-            c = self.lin.out_features
-            weight, bias, cp = self.lin.weight, self.lin.bias, half_width(c)
-            if cp != c:
-                weight = F.pad(weight, (0, 0, 0, cp - c))
-                bias = None if bias is None else F.pad(bias, (0, cp - c))
-            return _true_width(ops.attention(F.linear(x, weight, bias), graph), c)
+            return _true_width(ops.attention(_half_lin(x, self.lin), graph), self.lin.out_features)
         graph, shard = _graph_for(x, edge_index, True, LOOPS_REPLACE)
         h, c, table = _lin_aligned(x, self.lin, shard)
         if shard is not None:
@@ -385,28 +409,12 @@ class SNConv_plus(nn.Module):
 
     def forward(self, x, edge_index, epilogue=None, act_in=None, head=None, fold=None):
         """``epilogue`` / ``act_in`` / ``head`` / ``fold``: see SNConv.forward."""
+        loops, top_k, thr = bool(self.is_remove_self_loops), int(self.top_k), float(self.thr)
         if x.dtype in ops.HALF_DTYPES:
-            out, _ = _half_conv(x, edge_index, self.lin, True, bool(self.is_remove_self_loops), int(self.top_k),
-                                float(self.thr), epilogue, head, fold)
-            return out if self.bias is None else out + self.bias
-        graph, shard = _graph_for(x, edge_index, True, bool(self.is_remove_self_loops))
-        hint = self._filter_hint()
-        hint.poll()
-        unit = _unit_for(self.lin, graph, self.top_k, self.thr, hint)
-        h, c, table = _lin_aligned(x, self.lin, shard, unit, act_in, fold)
-        if shard is None and (unit.want_filter or unit.no_filter) and hint.due():
-            hint.probe(h.detach(), edge_index, float(self.thr), ops.filter_wanted(graph, h.size(1), int(self.top_k), 0.0))
-        if _fuse_head(head, graph, h, c, shard, int(self.top_k)):
-            return ops.aggregate(h, graph, int(self.top_k), float(self.thr), unit, None, self.bias, head)
-        if _fuse_epilogue(epilogue, h, c, shard):
-            return ops.aggregate(h, graph, int(self.top_k), float(self.thr), unit, epilogue, self.bias)
-        out = _true_width(_aggregate(h, graph, shard, int(self.top_k), float(self.thr), table, unit), c)
-        if self.bias is not None:
-            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
-                epilogue.bias = self.bias
-            else:
-                out = out + self.bias
-        return out
+            out, _ = _half_conv(x, edge_index, self.lin, True, loops, top_k, thr, epilogue=epilogue, head=head, fold=fold)
+            return _add_bias(out, self.bias)
+        graph, shard, unit, h, c, table = _sn_lin(self, x, edge_index, loops, top_k, thr, act_in, fold)
+        return _sn_aggregate(h, c, table, graph, shard, unit, top_k, thr, self.bias, epilogue, head)
 
 
 class _AdjLinearParams(nn.Module):
@@ -571,22 +579,15 @@ class SNConv_plus_plus(nn.Module):
                              "(the adjacency branch is Linear(num_nodes, C))")
         if part is None and self.w.shard_range is not None:
             raise ValueError("this layer holds a shard of w (built under a partition): run it under one")
+        loops, top_k, thr = bool(self.is_remove_self_loops), int(self.top_k), float(self.thr)
         if x.dtype in ops.HALF_DTYPES:
             # the half path: the adjacency branch is the fp32 kernel on an fp32 copy of w (its rows are gathered,
             # not normalised: no half kernel of its own), cast back; the blend in torch (models.py:134)
-            out_1, graph = _half_conv(x, edge_index, self.lin, True, bool(self.is_remove_self_loops), int(self.top_k),
-                                      float(self.thr), None, None, fold)
+            out_1, graph = _half_conv(x, edge_index, self.lin, True, loops, top_k, thr, fold=fold)
             wb = self.w.bias
             out_0 = ops.adj_linear(self.w.weight.float(), None if wb is None else wb.float(), graph).to(x.dtype)
-            out = self.beta * out_0 + (1 - self.beta) * out_1
-            return out if self.bias is None else out + self.bias
-        graph, shard = _graph_for(x, edge_index, True, bool(self.is_remove_self_loops))
-        hint = self._filter_hint()
-        hint.poll()
-        unit = _unit_for(self.lin, graph, self.top_k, self.thr, hint)
-        h, c, table = _lin_aligned(x, self.lin, shard, unit, act_in, fold)
-        if shard is None and (unit.want_filter or unit.no_filter) and hint.due():
-            hint.probe(h.detach(), edge_index, float(self.thr), ops.filter_wanted(graph, h.size(1), int(self.top_k), 0.0))
+            return _add_bias(self.beta * out_0 + (1 - self.beta) * out_1, self.bias)
+        graph, shard, unit, h, c, table = _sn_lin(self, x, edge_index, loops, top_k, thr, act_in, fold)
         if part is None:
             out_0 = ops.adj_linear(self.w.weight, self.w.bias, graph)
         else:
@@ -602,27 +603,20 @@ class SNConv_plus_plus(nn.Module):
                 # w sharded by node range: W^T rows travel like feature rows, over the flipped list
                 if self.w.shard_range != (part.row_begin, part.row_end):
                     raise ValueError("w was sharded for a different node range")
-                shard_f = _shard_for(flipped, part, True, bool(self.is_remove_self_loops))
+                shard_f = _shard_for(flipped, part, True, loops)
                 wt = self.w.weight.t()
                 w_table = shard_f.table(wt if wt.is_contiguous() else wt.contiguous())
                 out_0 = ops.gather_sum(w_table, self.w.bias, shard_f.graph)
             else:
                 # w.weight replicated ([C, N_total]): its gradient is each rank's partial sum,
                 # all-reduced with the other parameters (dist.allreduce_grads)
-                graph_out = GLOBAL_CACHE.get(flipped, part.n_total, True, bool(self.is_remove_self_loops),
-                                             row_range=(part.row_begin, part.row_end))
+                graph_out = GLOBAL_CACHE.get(flipped, part.n_total, True, loops, row_range=(part.row_begin, part.row_end))
                 out_0 = ops.adj_linear_partition(self.w.weight, self.w.bias, graph_out)
-        out_1 = _true_width(_aggregate(h, graph, shard, int(self.top_k), float(self.thr), table, unit), c)
+        out_1 = _sn_aggregate(h, c, table, graph, shard, unit, top_k, thr, None, None, None)      # (the blend takes them)
         if head is not None and part is None and self.bias is None:
             fused = ops.blend_head(out_0, out_1, self.beta, head)        # the head in the blend's own pass
             if fused is not None:
                 return fused
         if epilogue is not None and part is None and self.bias is None:
             return ops.blend(out_0, out_1, self.beta, epilogue)
-        out = ops.blend(out_0, out_1, self.beta)
-        if self.bias is not None:
-            if getattr(epilogue, "defer_bias", False):          # (models._Stack: the fused batch norm adds it)
-                epilogue.bias = self.bias
-            else:
-                out = out + self.bias
-        return out
+        return _add_bias(ops.blend(out_0, out_1, self.beta), self.bias, epilogue)

@@ -32,6 +32,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from . import ops
+from ._partition import current_partition, set_partition  # noqa: F401  (the active partition: a leaf module)
+
 
 @dataclass
 class Partition:
@@ -106,20 +109,6 @@ class Partition:
     @classmethod
     def edge_balanced(cls, rank, world, in_degree, **kw):
         return cls(rank, world, bounds=cls.edge_balanced_bounds(in_degree, world), **kw)
-
-
-_current: Optional[Partition] = None
-
-
-def set_partition(part: Optional[Partition]) -> None:
-    """Make the conv layers treat their inputs as the local shard of ``part``
-    (``None`` switches back to single-GPU behaviour)."""
-    global _current
-    _current = part
-
-
-def current_partition() -> Optional[Partition]:
-    return _current
 
 
 def check_features(x: torch.Tensor) -> None:
@@ -324,7 +313,6 @@ class _HaloAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows_local, table_ref, plan: HaloPlan, graph, top_k, thr):
-        from . import ops
         table = table_ref.t
         n_loc, c = plan.n_local, table.size(1)
         if rows_local.data_ptr() != table.data_ptr():
@@ -362,7 +350,6 @@ class _HaloAggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
         table, wsel = ctx.saved_tensors
         grad_table = ops.aggregate_backward(ctx.graph, table, grad_out.contiguous(), wsel, ctx.top_k)
         return return_halo_gradients(grad_table, ctx.plan), None, None, None, None, None

@@ -9,8 +9,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from .graph import LOOPS_REPLACE, Graph
-from .prop import HALF_DTYPES, _ops, prop_plain
+from ._partition import current_partition
+from ._rows import check_rows, check_whole_graph_with_loops
+from .graph import Graph
 
 MAX_HEADS = 16
 
@@ -18,13 +19,7 @@ MAX_HEADS = 16
 def gat_workspace(graph: Graph, channels: int, heads: int) -> torch.Tensor:
     """Scratch of the attention entries (``sngnn_gat_workspace_bytes``): the split rows' partials, the backward's
     edge records and score gradients - one buffer per (width, heads, stream), as ``Graph.workspace`` keeps them."""
-    key = ("gat", channels * heads, heads, _lib.stream(graph.device))
-    ws = graph._ws.get(key)
-    if ws is None:
-        nbytes = int(_lib.load().sngnn_gat_workspace_bytes(graph.handle, heads, channels))
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=graph.device)
-        graph._ws[key] = ws
-    return ws
+    return graph.scratch("sngnn_gat_workspace_bytes", heads, channels)
 
 
 # A/B switch of the fused attention kernels (csrc/gat.hip; tests flip it, SNGNN_GAT_FUSE=0 starts a process with it
@@ -35,19 +30,11 @@ FUSE_GAT = os.environ.get("SNGNN_GAT_FUSE", "1") != "0"
 def _check_gat(xp, att_src, att_dst, graph: Graph, heads: int):
     """The rows, the attention vectors and the graph of a GAT propagation: fp32 GPU rows [N, heads * C], one per node
     of the whole, loop-replaced graph (GATConv's edge list), and two vectors of heads * C elements."""
-    from . import dist as _dist
-    if xp.dtype in HALF_DTYPES:
-        raise ValueError(f"xp is {xp.dtype}: the graph attention has no half-width path (cast the rows to "
-                         "torch.float32)")
-    if _dist.current_partition() is not None or graph.num_nodes != graph.num_total_nodes:
-        raise ValueError("the graph attention runs on one GPU: node-range partitions are not implemented for it")
-    if not graph.add_loops or graph.remove_loops != LOOPS_REPLACE:
-        raise ValueError("the graph attention needs GATConv's edge list: a graph built with add_loops=True, "
-                         "remove_loops=LOOPS_REPLACE")
+    check_whole_graph_with_loops(graph, xp, "xp", "the graph attention", "GATConv's", current_partition())
     heads = int(heads)
     if not 1 <= heads <= MAX_HEADS:
         raise ValueError(f"heads must be in [1, {MAX_HEADS}], got {heads}")
-    xp = _ops()._check_rows(xp, graph.num_nodes, "xp")
+    xp = check_rows(xp, graph.num_nodes, "xp")
     if xp.size(1) % heads != 0:
         raise ValueError(f"xp must have shape [{graph.num_nodes}, heads * C], got {tuple(xp.shape)} with heads = {heads}")
     c = xp.size(1) // heads
@@ -88,7 +75,7 @@ class _GATPropagate(torch.autograd.Function):
         want_x, want_att = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         if not (want_x or want_att):
             return None, None, None, None, None, None
-        g = _ops()._check_rows(g.contiguous(), graph.num_nodes, "grad_out")
+        g = check_rows(g.contiguous(), graph.num_nodes, "grad_out")
         c = xp.size(1) // heads
         gx = torch.empty_like(xp) if want_x else None
         gatt = torch.empty((2,) + tuple(att_src.shape), dtype=torch.float32, device=xp.device) if want_att else None
@@ -98,13 +85,14 @@ class _GATPropagate(torch.autograd.Function):
                 None, None, None)
 
 
+def _build_plain_edges(graph: Graph, _key):
+    _, tgt, src = graph.csr_entries()
+    return src.long(), tgt.long()
+
+
 def _plain_edges(graph: Graph):
-    """(src, tgt) int64 [E'] per CSR entry, kept with the graph (``prop.prop_plain`` builds them once)."""
-    hit = graph._ws.get("gat_plain")
-    if hit is None:
-        _, (_, tgt, src) = prop_plain(graph)
-        hit = graph._ws["gat_plain"] = (src.long(), tgt.long())
-    return hit
+    """(src, tgt) int64 [E'] per CSR entry, kept with the graph."""
+    return graph.cached("gat_plain", _build_plain_edges)
 
 
 def _gat_plain(xp, att_src, att_dst, graph, heads, slope):

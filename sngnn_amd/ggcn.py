@@ -76,17 +76,12 @@ class _AdjStructure:
 
     def full(self):
         """The structure of ALL entries of adj, diagonal included (the plain propagation of use_sign=False,
-        models.py:1544-1549): (graph, perm with ``coef_csr = coef_entries[perm]``, (csc_eid, tgt, src) of
-        ``ops.weighted_propagate``).  Built on first use."""
+        models.py:1544-1549): (graph, perm with ``coef_csr = coef_entries[perm]``, the graph's ``csr_entries()`` - the
+        ``aux`` of ``ops.weighted_propagate``).  Built on first use."""
         if self._full is None:
             g = Graph(self._ei, self._n, False, False)
-            dev = self._ei.device
-            perm = torch.from_numpy(g.array("eid").astype("int64")).to(dev)
-            src = torch.from_numpy(g.array("col")).to(dev)                       # int32 [E'] source of each CSR entry
-            rowptr = torch.from_numpy(g.array("rowptr").astype("int64")).to(dev)
-            tgt = torch.repeat_interleave(torch.arange(self._n, device=dev, dtype=torch.int32), rowptr[1:] - rowptr[:-1])
-            csc_eid = torch.from_numpy(g.array("csc_eid").astype("int64")).to(dev)
-            self._full = (g, perm, (csc_eid, tgt.contiguous(), src.contiguous()))
+            perm = torch.from_numpy(g.array("eid").astype("int64")).to(self._ei.device)
+            self._full = (g, perm, g.csr_entries())
         return self._full
 
 

@@ -17,8 +17,7 @@ from . import _lib
 
 _ARRAYS = {"rowptr": 0, "col": 1, "eid": 2, "cscptr": 3, "csc_eid": 4, "rperm": 5}
 
-
-LOOPS_REPLACE = 2      # SNGNN_LOOPS_REPLACE: drop the original loops, then append one per node
+LOOPS_REPLACE = _lib.LOOPS_REPLACE
 
 
 class Graph:
@@ -53,36 +52,45 @@ class Graph:
         self.max_in_degree = int(lib.sngnn_graph_max_in_degree(handle))
         self.num_fused_nodes = int(lib.sngnn_graph_num_fused_nodes(handle))    # in- and out-degree <= 16 (node-centric backward)
         self.src_min = int(lib.sngnn_graph_src_min(handle))
-        self._ws: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._ws: Dict[Tuple, object] = {}          # everything cached per graph: scratch() and cached()
 
     @property
     def handle(self):
         return self._h
 
-    def workspace(self, channels: int) -> torch.Tensor:
-        """Scratch for forward/backward at ``channels``: one buffer per (width, stream), so
-        calls on the same graph from different streams never share scratch (the entry
-        points are re-entrant per stream).  Allocated on first use: ``GraphedEpoch`` runs an
-        eager pass on the very stream it then captures on, so the capture finds its buffers."""
-        key = (channels, _lib.stream(self.device))
+    def scratch(self, entry: str, a=None, b=None) -> torch.Tensor:
+        """Scratch sized by the library's ``entry(handle[, a[, b]])``: one uint8 buffer per (entry, a, b, stream), so
+        calls on the same graph from different streams never share scratch (the entry points are re-entrant per
+        stream).  Allocated on first use - ``GraphedEpoch`` runs an eager pass on the very stream it then captures on,
+        so the capture finds its buffers - and kept as long as the graph lives."""
+        key = (entry, a, b, _lib.stream(self.device))
         ws = self._ws.get(key)
         if ws is None:
-            nbytes = int(_lib.load().sngnn_graph_workspace_bytes(self._h, channels))
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
+            nbytes = int(getattr(_lib.load(), entry)(self._h, *(p for p in (a, b) if p is not None)))
+            ws = self._ws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
         return ws
 
+    def cached(self, key, build):
+        """Any other object kept with the graph: ``build(graph, key)`` on first use, that object from then on."""
+        hit = self._ws.get(key)
+        if hit is None:
+            hit = self._ws[key] = build(self, key)
+        return hit
+
+    def workspace(self, channels: int) -> torch.Tensor:
+        """Scratch for forward/backward at ``channels`` (one buffer per width and stream: :meth:`scratch`)."""
+        return self.scratch("sngnn_graph_workspace_bytes", channels)
+
     def head_workspace(self) -> torch.Tensor:
-        """Scratch of the classification head inside this graph's forward (``sngnn_epilogue_t.head_workspace``):
-        one buffer per stream, owned by the graph like :meth:`workspace` - a captured epoch that holds the
-        graph holds the buffer its launches point into."""
-        key = ("head", _lib.stream(self.device))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(_lib.load().sngnn_agg_head_workspace_bytes(self._h))
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        return ws
+        """Scratch of the classification head inside this graph's forward (``sngnn_epilogue_t.head_workspace``): a
+        captured epoch that holds the graph holds the buffer its launches point into."""
+        return self.scratch("sngnn_agg_head_workspace_bytes")
+
+    def csr_entries(self):
+        """(csc_eid int64 [E'], tgt int32 [E'], src int32 [E']) on the device: the CSC -> CSR map and the row and
+        column of every CSR entry - the ``aux`` of ``ops.weighted_propagate``.  Built on first use (copies the
+        structure arrays through the host once)."""
+        return self.cached("csr_entries", _csr_entries)
 
     def array(self, name: str) -> np.ndarray:
         """Host copy of one of the structure arrays (tests / inspection)."""
@@ -103,6 +111,16 @@ class Graph:
             except Exception:
                 pass
             self._h = None
+
+
+def _csr_entries(graph: Graph, _key):
+    dev = graph.device
+    src = torch.from_numpy(graph.array("col")).to(dev)
+    rowptr = torch.from_numpy(graph.array("rowptr").astype("int64")).to(dev)
+    tgt = torch.repeat_interleave(torch.arange(graph.num_nodes, device=dev, dtype=torch.int32),
+                                  rowptr[1:] - rowptr[:-1])
+    csc_eid = torch.from_numpy(graph.array("csc_eid").astype("int64")).to(dev)
+    return csc_eid, tgt.contiguous(), src.contiguous()
 
 
 class GraphCache:

@@ -73,7 +73,7 @@ class _Stack(nn.Module):
         for i, lin in enumerate(self.lins[:-1]):
             if fusable:
                 epi = ops.HiddenEpilogue(True, self.dropout.p, self.training, None if seeds is None else seeds[i:i + 1])
-                x = lin(x, edge_index, epi, act)
+                x = lin(x, edge_index, epilogue=epi, act_in=act)
                 if epi.applied:
                     act = epi
                     continue
@@ -87,9 +87,9 @@ class _Stack(nn.Module):
                 x = self.bns[i](x) if part is None else sn_dist.sync_batch_norm(self.bns[i], x, part)
             x = self.dropout(x)
         if takes_head:
-            return self.lins[-1](x, edge_index, None, act if fusable else None, head)
+            return self.lins[-1](x, edge_index, act_in=act if fusable else None, head=head)
         if fusable and act is not None:
-            return self.lins[-1](x, edge_index, None, act)
+            return self.lins[-1](x, edge_index, act_in=act)
         return self.lins[-1](x, edge_index)
 
     def _forward_logits_bn_eval(self, x, edge_index, head):
@@ -97,13 +97,13 @@ class _Stack(nn.Module):
         fold = None
         for i, lin in enumerate(self.lins[:-1]):
             epi = ops.HiddenEpilogue(True, 0.0, False)                   # conv bias + relu in the stores
-            y = lin(x, edge_index, epi, None, None, fold)
+            y = lin(x, edge_index, epilogue=epi, fold=fold)
             if epi.applied:
                 x, fold = y, LinFold.of_batch_norm(self.bns[i])          # the norm rides in the next lin
             else:                                                        # (a shape the epilogue does not take)
                 x, fold = self.bns[i](F.relu(y, inplace=True)), None
         takes_head = head is not None and isinstance(self.lins[-1], (SNConv, SNConv_plus))
-        return self.lins[-1](x, edge_index, None, None, head if takes_head else None, fold)
+        return self.lins[-1](x, edge_index, head=head if takes_head else None, fold=fold)
 
     def _bn_train_fusable(self, x) -> bool:
         """Whether a training forward's hidden transitions run as ``ops.batch_norm_act``: one GPU, fp32 features and
@@ -135,13 +135,13 @@ class _Stack(nn.Module):
             # hands over its bias instead of adding it (``defer_bias``): the kernels add it.
             epi = ops.HiddenEpilogue(True, 0.0, False)
             epi.defer_bias = True
-            y = lin(x, edge_index, epi)
+            y = lin(x, edge_index, epilogue=epi)
             if epi.applied:
                 x = ops.batch_norm_act(y, self.bns[i], None, p, None, seed, epi)
             else:
                 x = ops.batch_norm_act(y, self.bns[i], epi.bias, p, None, seed)
         if head is not None:
-            return self.lins[-1](x, edge_index, None, None, head)
+            return self.lins[-1](x, edge_index, head=head)
         return self.lins[-1](x, edge_index)
 
     def forward(self, data):

@@ -13,34 +13,31 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._rows import HALF_DTYPES, check_flat as _check_flat, check_grad_dtype as _check_grad_dtype, check_rows as _check_rows
 from .batchnorm import _BatchNormAct, batch_norm_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
 from .gat import gat_propagate  # noqa: F401  (csrc/gat.hip)
 from .graph import Graph
-from .prop import appnp_propagate, gpr_propagate  # noqa: F401  (csrc/prop.hip)
-
-
-# storage types of the half path (sngnn_agg_forward_half / sngnn_agg_backward_half, sngnn_attn_*_half,
-# sngnn_signed_*_half): the fp32 operator on h.float(), only the stored rows rounded once to the type
-HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
-
-
-def _check_rows(t: torch.Tensor, n: int, what: str, half: bool = False) -> torch.Tensor:
-    if t.dtype != torch.float32 and not (half and t.dtype in HALF_DTYPES):
-        if half:
-            raise ValueError(f"{what} must be float32, float16 or bfloat16, got {t.dtype}")
-        raise ValueError(f"{what} must be float32 (the reference path is fp32 only)")
-    if not t.is_cuda:
-        raise ValueError(f"{what} must live on the GPU (there is no CPU path)")
-    if t.dim() != 2 or t.size(0) != n:
-        raise ValueError(f"{what} must have shape [{n}, C], got {tuple(t.shape)}")
-    if not 1 <= t.size(1) <= _lib.MAX_CHANNELS:
-        raise ValueError(f"{what}: C must be in [1, {_lib.MAX_CHANNELS}]")
-    return t.contiguous()
+from .prop import _WeightedPropagate, appnp_propagate, gpr_propagate, weighted_propagate  # noqa: F401  (csrc/prop.hip)
 
 
 def _k(top_k: Optional[int]) -> int:
     """The C ABI's top_k: -1 = no selection."""
     return -1 if top_k is None else int(top_k)
+
+
+def _forward_buffers(graph: Graph, like: torch.Tensor, c: int, k: int, need_grad: bool, want_selection: bool = False):
+    """What a forward writes: (out [N, C] of ``like``'s dtype, wsel [E'] and inv [N] with ``need_grad``, sel_src and
+    sel_w [N, k] with ``want_selection``; None otherwise)."""
+    n, dev = graph.num_nodes, like.device
+    out = torch.empty((n, c), dtype=like.dtype, device=dev)
+    wsel = inv = sel_src = sel_w = None
+    if need_grad:
+        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=dev)
+        inv = torch.empty(n, dtype=torch.float32, device=dev)
+    if want_selection:
+        sel_src = torch.empty((n, k), dtype=torch.int32, device=dev)
+        sel_w = torch.empty((n, k), dtype=torch.float32, device=dev)
+    return out, wsel, inv, sel_src, sel_w
 
 
 def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: float, *,
@@ -49,22 +46,14 @@ def aggregate_forward(graph: Graph, h: torch.Tensor, top_k: Optional[int], thr: 
     unless requested.  ``top_k=None`` is SNConv (no selection).  A float16 / bfloat16 ``h`` takes
     the half path: ``out`` in h's dtype (the fp32 operator on h.float(), scored on the fly, its
     rows rounded once), everything else fp32."""
-    n = graph.num_nodes
     h = _check_rows(h, graph.num_total_nodes, "h", half=True)
     c = h.size(1)
     k = _k(top_k)
     if top_k is not None and k < 0:
         raise ValueError("top_k must be >= 0")
-    out = torch.empty((n, c), dtype=h.dtype, device=h.device)
-    wsel = inv = sel_src = sel_w = None
-    if save_for_backward:
-        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=h.device)
-        inv = torch.empty(n, dtype=torch.float32, device=h.device)
-    if want_selection:
-        if k < 0:
-            raise ValueError("the selection is only defined for top_k >= 0")
-        sel_src = torch.empty((n, k), dtype=torch.int32, device=h.device)
-        sel_w = torch.empty((n, k), dtype=torch.float32, device=h.device)
+    if want_selection and k < 0:
+        raise ValueError("the selection is only defined for top_k >= 0")
+    out, wsel, inv, sel_src, sel_w = _forward_buffers(graph, h, c, k, save_for_backward, want_selection)
     ws = graph.workspace(c)
     if h.dtype in HALF_DTYPES:
         _lib.call("sngnn_agg_forward_half", h.device, graph.handle, h, HALF_DTYPES[h.dtype], c, k, float(thr),
@@ -150,15 +139,8 @@ def aggregate_forward_normalized(graph: Graph, n: torch.Tensor, nrm: torch.Tenso
 def _prepared(graph: Graph, n, nrm, filt, top_k, thr, need_grad: bool, want_selection: bool):
     """The one caller of ``sngnn_agg_forward_prepared``: returns (out, wsel, sel_src, sel_w), ``wsel`` only with
     ``need_grad`` and the selection only with ``want_selection``."""
-    rows, c, k = graph.num_nodes, n.size(1), _k(top_k)
-    out = torch.empty((rows, c), dtype=torch.float32, device=n.device)
-    wsel = inv = sel_src = sel_w = None
-    if need_grad:
-        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=n.device)
-        inv = torch.empty(rows, dtype=torch.float32, device=n.device)
-    if want_selection:
-        sel_src = torch.empty((rows, k), dtype=torch.int32, device=n.device)
-        sel_w = torch.empty((rows, k), dtype=torch.float32, device=n.device)
+    c, k = n.size(1), _k(top_k)
+    out, wsel, inv, sel_src, sel_w = _forward_buffers(graph, n, c, k, need_grad, want_selection)
     _lib.call("sngnn_agg_forward_prepared", n.device, graph.handle, n, nrm, filt, c, k, float(thr), out, wsel, inv,
               sel_src, sel_w, graph.workspace(c))
     return out, wsel, sel_src, sel_w
@@ -239,6 +221,10 @@ class HiddenEpilogue:
         self.applied = False
         self.premasked = False
         self.scale = 1.0
+        # a layer that does NOT take the store epilogue hands its bias to the owner instead of adding it
+        # (``defer_bias``, set by models._Stack where the fused batch norm adds it): the layer leaves it in ``bias``
+        self.defer_bias = False
+        self.bias = None
 
     @property
     def drops(self) -> bool:
@@ -391,13 +377,11 @@ def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optiona
     lib = _lib.load()
     h = _check_rows(h, graph.num_total_nodes, "h")
     n, c = graph.num_nodes, h.size(1)
-    out = torch.empty((n, c), dtype=torch.float32, device=h.device)
-    wsel = inv = keep = kbits = None
+    k = _k(top_k)
+    out, wsel, inv, _, _ = _forward_buffers(graph, h, c, k, need_grad and not bits)
+    keep = kbits = None
     if need_grad and bits:
         kbits = torch.empty(max(int(lib.sngnn_graph_kept_bits_bytes(graph.handle)), 16), dtype=torch.uint8, device=h.device)
-    elif need_grad:
-        wsel = torch.empty(graph.num_edges, dtype=torch.float32, device=h.device)
-        inv = torch.empty(n, dtype=torch.float32, device=h.device)
     if epi is None:
         epi = HiddenEpilogue(False, 0.0, False)          # (a plain forward that saves the bits)
     epi.scale = 1.0
@@ -416,7 +400,7 @@ def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optiona
         bias = bias.detach().contiguous()
     st = _lib.Epilogue(_lib.ptr(bias), _lib.ptr(keep), float(epi.scale), int(epi.relu), _lib.ptr(seed), float(epi.p),
                        _lib.ptr(kbits))
-    if unit is not None and getattr(unit, "no_filter", False):
+    if unit is not None and unit.no_filter:
         st.no_filter = 1
     if head is not None:
         if head.y.numel() != n or head.sel.numel() != n or head.y.device != h.device or head.sel.device != h.device:
@@ -428,7 +412,7 @@ def _forward_epilogue(graph: Graph, h, unit, top_k, thr, need_grad, epi: Optiona
         st.head_sets, st.head_out_mode = head.sets, head.out_mode
         st.head_n_a, st.head_n_b = head.n_a, head.n_b
         st.head_metrics, st.head_workspace = head.metrics.data_ptr(), hws.data_ptr()
-    k, thr, epi_ref, ws = _k(top_k), float(thr), ctypes.byref(st), graph.workspace(c)
+    thr, epi_ref, ws = float(thr), ctypes.byref(st), graph.workspace(c)
     if unit is not None and unit.n is not None:
         _lib.call("sngnn_agg_forward_prepared_epilogue", h.device, graph.handle, unit.n, unit.nrm, unit.filt, c, k, thr,
                   epi_ref, out, wsel, inv, ws)
@@ -467,12 +451,6 @@ def attention_forward(graph: Graph, h: torch.Tensor, save_for_backward: bool = T
     else:
         _lib.call("sngnn_attn_forward", h.device, graph.handle, h, c, out, alpha, graph.workspace(c))
     return out, alpha
-
-
-def _check_grad_dtype(grad_out: torch.Tensor, rows: torch.Tensor, what: str) -> None:
-    """``grad_out`` of a half call has the rows' dtype; of an fp32 call, float32."""
-    if grad_out.dtype != rows.dtype:
-        raise ValueError(f"grad_out must have {what}'s dtype {rows.dtype}, got {grad_out.dtype}")
 
 
 def attention_backward(graph: Graph, h: torch.Tensor, grad_out: torch.Tensor,
@@ -589,50 +567,6 @@ class _SignedPropagate(torch.autograd.Function):
 def signed_propagate(wh: torch.Tensor, coef: torch.Tensor, c2: torch.Tensor, graph: Graph) -> torch.Tensor:
     """Differentiable signed cosine propagation: [N_total, C] -> [N, C] (see ``_SignedPropagate``)."""
     return _SignedPropagate.apply(wh, coef, c2, graph)
-
-
-class _WeightedPropagate(torch.autograd.Function):
-    """``torch.sparse.mm(A, X)`` for a sparse ``A`` whose pattern is a device graph (GGCNlayer_SP's plain
-    propagation, models.py:1544-1549): ``out[i] = sum_e w_e X[src_e]`` over the in-edges of i, with autograd
-    through X (the transpose gather-sum) and through the per-entry weights (``<G_i, X_j>`` per entry) -
-    ``sngnn_weighted_gather_sum_rows`` / ``_scatter_sum_rows`` / ``sngnn_pair_dot_rows``: gathers with a fixed
-    order, no atomics.  ``w_csr`` [E'] in the graph's CSR order; ``aux`` = (csc_eid int64 [E'], tgt int32 [E'],
-    src int32 [E']) - the graph's CSC -> CSR map and the CSR entries' rows and columns, built once per graph."""
-
-    @staticmethod
-    def forward(ctx, x, w_csr, graph, aux):
-        x = _check_rows(x, graph.num_total_nodes, "x")
-        c = x.size(1)
-        if w_csr.dtype != torch.float32 or w_csr.numel() != graph.num_edges or not w_csr.is_cuda:
-            raise ValueError("w_csr must be a float32 GPU tensor with one entry per edge of the graph")
-        w_csr = w_csr.contiguous()
-        out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=x.device)
-        _lib.call("sngnn_weighted_gather_sum_rows", x.device, graph.handle, x, w_csr, c, out, graph.workspace(c))
-        ctx.graph, ctx.aux = graph, aux
-        ctx.save_for_backward(x, w_csr)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w_csr = ctx.saved_tensors
-        graph = ctx.graph
-        csc_eid, tgt, src = ctx.aux
-        g = _check_rows(g.contiguous(), graph.num_nodes, "grad_out")
-        c = x.size(1)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            w_csc = w_csr.index_select(0, csc_eid)
-            _lib.call("sngnn_weighted_scatter_sum_rows", x.device, graph.handle, g, w_csc, c, gx, graph.workspace(c))
-        if ctx.needs_input_grad[1]:
-            gw = torch.empty_like(w_csr)
-            _lib.call("sngnn_pair_dot_rows", x.device, g, tgt, x, src, w_csr.numel(), c, gw)
-        return gx, gw, None, None
-
-
-def weighted_propagate(x: torch.Tensor, w_csr: torch.Tensor, graph: Graph, aux) -> torch.Tensor:
-    """Differentiable weighted gather-sum over a graph's in-edges (see ``_WeightedPropagate``)."""
-    return _WeightedPropagate.apply(x, w_csr, graph, aux)
 
 
 def adj_linear_forward(graph: Graph, wt: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
@@ -977,18 +911,6 @@ def blend(out0: torch.Tensor, out1: torch.Tensor, beta: torch.Tensor,
 
 
 GGCN_ACT, GGCN_PREV_ELU = 1, 2          # SNGNN_GGCN_*: the flags of sngnn_ggcn_transition_forward / _backward
-
-
-def _check_flat(t: torch.Tensor, like: Optional[torch.Tensor], what: str) -> torch.Tensor:
-    if not torch.is_tensor(t) or t.dtype != torch.float32:
-        raise ValueError(f"{what} must be a float32 tensor (the fused GGCN transition is fp32 only)")
-    if not t.is_cuda:
-        raise ValueError(f"{what} must live on the GPU (there is no CPU path)")
-    if not t.is_contiguous():
-        raise ValueError(f"{what} must be contiguous, got shape {tuple(t.shape)} with strides {t.stride()}")
-    if like is not None and (t.shape != like.shape or t.device != like.device):
-        raise ValueError(f"{what} must have prop's shape {tuple(like.shape)} and device, got {tuple(t.shape)} on {t.device}")
-    return t
 
 
 class _GGCNTransition(torch.autograd.Function):

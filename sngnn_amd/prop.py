@@ -1,6 +1,7 @@
 """GPRGNN / APPNP propagation with the GCN-normalised adjacency: the autograd seam over ``sngnn_prop_*``
-(csrc/prop.hip) and the per-graph state it needs.  Re-exported by ``sngnn_amd.ops`` (``ops.gpr_propagate``,
-``ops.appnp_propagate``)."""
+(csrc/prop.hip) and the per-graph state it needs, and the plain weighted gather-sum both their unfused form and GGCN's
+plain branch run.  Re-exported by ``sngnn_amd.ops`` (``ops.gpr_propagate``, ``ops.appnp_propagate``,
+``ops.weighted_propagate``)."""
 from __future__ import annotations
 
 import os
@@ -8,57 +9,38 @@ import os
 import torch
 
 from . import _lib
-from .graph import LOOPS_REPLACE, Graph
+from ._partition import current_partition
+from ._rows import check_rows, check_whole_graph_with_loops
+from .graph import Graph
 
-HALF_DTYPES = (torch.float16, torch.bfloat16)
-
-
-def _ops():
-    """``sngnn_amd.ops`` (it re-exports this module's operators, so it is looked up at call time)."""
-    from . import ops
-    return ops
+def _build_dinv(graph: Graph, _key) -> torch.Tensor:
+    dinv = torch.empty(graph.num_nodes, dtype=torch.float32, device=graph.device)
+    _lib.call("sngnn_prop_dinv", graph.device, graph.handle, dinv)
+    return dinv
 
 
 def prop_dinv(graph: Graph) -> torch.Tensor:
     """``deg^-1/2`` of gcn_norm, float32 [N], from the graph's own rowptr (``sngnn_prop_dinv``): built on first
     use, kept with the graph.  Needs the loop-replaced, unpartitioned graph (the C entry says so otherwise)."""
-    dinv = graph._ws.get("prop_dinv")
-    if dinv is None:
-        dinv = torch.empty(graph.num_nodes, dtype=torch.float32, device=graph.device)
-        _lib.call("sngnn_prop_dinv", graph.device, graph.handle, dinv)
-        graph._ws["prop_dinv"] = dinv
-    return dinv
+    return graph.cached("prop_dinv", _build_dinv)
 
 
 def prop_workspace(graph: Graph, channels: int, hops: int) -> torch.Tensor:
     """Scratch of the propagation entries (``sngnn_prop_workspace_bytes``): the two scaled iterates, the split
     rows' partials and the dot partials - one buffer per (width, hops, stream), as ``Graph.workspace`` keeps them."""
-    key = ("prop", channels, hops, _lib.stream(graph.device))
-    ws = graph._ws.get(key)
-    if ws is None:
-        nbytes = int(_lib.load().sngnn_prop_workspace_bytes(graph.handle, channels, hops))
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=graph.device)
-        graph._ws[key] = ws
-    return ws
+    return graph.scratch("sngnn_prop_workspace_bytes", channels, hops)
+
+
+def _build_plain(graph: Graph, _key):
+    aux = _, tgt, src = graph.csr_entries()
+    dinv = prop_dinv(graph)
+    return (dinv[src.long()] * dinv[tgt.long()]).contiguous(), aux
 
 
 def prop_plain(graph: Graph):
     """What the unfused propagation (``SNGNN_GPR_FUSE=0``) reads: ``(norm, aux)`` with ``norm`` float32 [E'] =
-    ``dinv[src] * dinv[tgt]`` per CSR entry and ``aux`` the (csc_eid, tgt, src) of ``ops.weighted_propagate``.
-    Built on first use (copies the structure arrays through the host once)."""
-    hit = graph._ws.get("prop_plain")
-    if hit is None:
-        dev = graph.device
-        src = torch.from_numpy(graph.array("col")).to(dev)
-        rowptr = torch.from_numpy(graph.array("rowptr").astype("int64")).to(dev)
-        tgt = torch.repeat_interleave(torch.arange(graph.num_nodes, device=dev, dtype=torch.int32),
-                                      rowptr[1:] - rowptr[:-1])
-        csc_eid = torch.from_numpy(graph.array("csc_eid").astype("int64")).to(dev)
-        dinv = prop_dinv(graph)
-        norm = dinv[src.long()] * dinv[tgt.long()]
-        hit = (norm.contiguous(), (csc_eid, tgt.contiguous(), src.contiguous()))
-        graph._ws["prop_plain"] = hit
-    return hit
+    ``dinv[src] * dinv[tgt]`` per CSR entry and ``aux`` = ``graph.csr_entries()``.  Built on first use."""
+    return graph.cached("prop_plain", _build_plain)
 
 
 # A/B switch of the fused normalised-adjacency hops (csrc/prop.hip; tests flip it, SNGNN_GPR_FUSE=0 starts a process
@@ -70,17 +52,9 @@ FUSE_GPR = os.environ.get("SNGNN_GPR_FUSE", "1") != "0"
 def _check_prop(x: torch.Tensor, graph: Graph, what: str) -> torch.Tensor:
     """The rows and the graph of a normalised-adjacency propagation: fp32 GPU rows, one per node of the whole,
     loop-replaced graph (gcn_norm's edge list)."""
-    from . import dist as _dist
-    if x.dtype in HALF_DTYPES:
-        raise ValueError(f"{what} is {x.dtype}: the normalised-adjacency propagation has no half-width path "
-                         "(cast the rows to torch.float32)")
-    if _dist.current_partition() is not None or graph.num_nodes != graph.num_total_nodes:
-        raise ValueError("the normalised-adjacency propagation runs on one GPU: node-range partitions are not "
-                         "implemented for it")
-    if not graph.add_loops or graph.remove_loops != LOOPS_REPLACE:
-        raise ValueError("the normalised-adjacency propagation needs gcn_norm's edge list: a graph built with "
-                         "add_loops=True, remove_loops=LOOPS_REPLACE")
-    return _ops()._check_rows(x, graph.num_nodes, what)
+    check_whole_graph_with_loops(graph, x, what, "the normalised-adjacency propagation", "gcn_norm's",
+                                 current_partition())
+    return check_rows(x, graph.num_nodes, what)
 
 
 def _gamma32(gamma: torch.Tensor, device) -> torch.Tensor:
@@ -116,7 +90,7 @@ class _GPRPropagate(torch.autograd.Function):
     def backward(ctx, g):
         x, g32 = ctx.saved_tensors
         graph = ctx.graph
-        g = _ops()._check_rows(g.contiguous(), graph.num_nodes, "grad_out")
+        g = check_rows(g.contiguous(), graph.num_nodes, "grad_out")
         k, c = g32.numel() - 1, x.size(1)
         want_x, want_gamma = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if k == 0:
@@ -130,9 +104,53 @@ class _GPRPropagate(torch.autograd.Function):
         return gx, None if gg is None else gg.to(ctx.gamma_dtype), None
 
 
+class _WeightedPropagate(torch.autograd.Function):
+    """``torch.sparse.mm(A, X)`` for a sparse ``A`` whose pattern is a device graph (GGCNlayer_SP's plain
+    propagation, models.py:1544-1549): ``out[i] = sum_e w_e X[src_e]`` over the in-edges of i, with autograd
+    through X (the transpose gather-sum) and through the per-entry weights (``<G_i, X_j>`` per entry) -
+    ``sngnn_weighted_gather_sum_rows`` / ``_scatter_sum_rows`` / ``sngnn_pair_dot_rows``: gathers with a fixed
+    order, no atomics.  ``w_csr`` [E'] in the graph's CSR order; ``aux`` = (csc_eid int64 [E'], tgt int32 [E'],
+    src int32 [E']) - the graph's CSC -> CSR map and the CSR entries' rows and columns, built once per graph."""
+
+    @staticmethod
+    def forward(ctx, x, w_csr, graph, aux):
+        x = check_rows(x, graph.num_total_nodes, "x")
+        c = x.size(1)
+        if w_csr.dtype != torch.float32 or w_csr.numel() != graph.num_edges or not w_csr.is_cuda:
+            raise ValueError("w_csr must be a float32 GPU tensor with one entry per edge of the graph")
+        w_csr = w_csr.contiguous()
+        out = torch.empty((graph.num_nodes, c), dtype=torch.float32, device=x.device)
+        _lib.call("sngnn_weighted_gather_sum_rows", x.device, graph.handle, x, w_csr, c, out, graph.workspace(c))
+        ctx.graph, ctx.aux = graph, aux
+        ctx.save_for_backward(x, w_csr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w_csr = ctx.saved_tensors
+        graph = ctx.graph
+        csc_eid, tgt, src = ctx.aux
+        g = check_rows(g.contiguous(), graph.num_nodes, "grad_out")
+        c = x.size(1)
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            w_csc = w_csr.index_select(0, csc_eid)
+            _lib.call("sngnn_weighted_scatter_sum_rows", x.device, graph.handle, g, w_csc, c, gx, graph.workspace(c))
+        if ctx.needs_input_grad[1]:
+            gw = torch.empty_like(w_csr)
+            _lib.call("sngnn_pair_dot_rows", x.device, g, tgt, x, src, w_csr.numel(), c, gw)
+        return gx, gw, None, None
+
+
+def weighted_propagate(x: torch.Tensor, w_csr: torch.Tensor, graph: Graph, aux) -> torch.Tensor:
+    """Differentiable weighted gather-sum over a graph's in-edges (see ``_WeightedPropagate``)."""
+    return _WeightedPropagate.apply(x, w_csr, graph, aux)
+
+
 def _plain_hop(x, graph):
     norm, aux = prop_plain(graph)
-    return _ops().weighted_propagate(x, norm, graph, aux)
+    return weighted_propagate(x, norm, graph, aux)
 
 
 def gpr_propagate(x: torch.Tensor, gamma: torch.Tensor, graph: Graph) -> torch.Tensor:
@@ -150,17 +168,17 @@ def gpr_propagate(x: torch.Tensor, gamma: torch.Tensor, graph: Graph) -> torch.T
     return hidden
 
 
+def _build_coefficients(graph: Graph, key) -> torch.Tensor:
+    coef = torch.empty(2, dtype=torch.float32, device=graph.device)
+    coef[0].fill_(key[1])
+    coef[1].fill_(1.0 - key[1])
+    return coef
+
+
 def _appnp_coefficients(graph: Graph, alpha: float) -> torch.Tensor:
     """(alpha, 1 - alpha) as a device tensor kept with the graph (next to ``dinv``: it lives as long as the graph does),
     filled without a host-to-device copy (nothing synchronises)."""
-    key = ("appnp_coef", float(alpha))
-    coef = graph._ws.get(key)
-    if coef is None:
-        coef = torch.empty(2, dtype=torch.float32, device=graph.device)
-        coef[0].fill_(float(alpha))
-        coef[1].fill_(1.0 - float(alpha))
-        graph._ws[key] = coef
-    return coef
+    return graph.cached(("appnp_coef", float(alpha)), _build_coefficients)
 
 
 class _APPNPPropagate(torch.autograd.Function):
@@ -185,7 +203,7 @@ class _APPNPPropagate(torch.autograd.Function):
     def backward(ctx, g):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        g = _ops()._check_rows(g.contiguous(), ctx.graph.num_nodes, "grad_out")
+        g = check_rows(g.contiguous(), ctx.graph.num_nodes, "grad_out")
         return _APPNPPropagate._run(g, ctx.graph, ctx.k, ctx.alpha, 1), None, None, None
 
 

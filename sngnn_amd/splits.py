@@ -335,7 +335,7 @@ class ReplicaBatch(nn.Module):
         if self.kind is not SNGNN:
             unit = ops.UnitRows(ops.filter_wanted(g, self.Cp, self.top_k, self.thr))
         h = _ReplicaLinear.apply(data.x.contiguous(), self.lin_weight, self.lin_bias, r, unit)
-        out = ops.aggregate(h, g, self.top_k, self.thr, unit)
+        out = ops.aggregate(h, g, self.top_k, self.thr, unit=unit)
         if self.Cp != c:
             out = out[:, :c]
         if self.kind is SNGNN:

@@ -17,6 +17,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn.functional as F
 
+from . import ops
 from .synth import Data
 
 
@@ -114,7 +115,6 @@ class GraphedEpoch:
         # both, bit for bit.  False replays the reference's two passes.
         self.share_eval_forward = share_eval_forward
         dev = data.x.device
-        from . import ops
         self._ops = ops
         self.mask = {k: getattr(data, k + "_mask").to(torch.uint8).contiguous()
                      for k in ("train", "val", "test")}
