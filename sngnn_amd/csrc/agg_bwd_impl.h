@@ -69,7 +69,7 @@ struct BwdArgs {
     int role_mask;                // measurement aid (sngnn_tuning_set knob 4): bit 0 wave-per-node items, bit 1 fused items
     int top_k;                    // the forward's top_k when the caller gave it (at most that many kept in-edges
                                   // per row), else <= 0
-    // kept bits written by the forward itself (common.h "kbits" layout; agg_fwd_impl.h): no k_pack_kept
+    // kept bits written by the forward itself (common.h "kbits" layout; agg_fwd_args.h): no k_pack_kept
     // launch.  Small rows: halfword at the row id; wave rows / tasks: 128-bit blocks; out-edges by csc_bit.
     const unsigned *kbits;
     const int32_t *csc_bit;
@@ -111,7 +111,7 @@ __device__ __forceinline__ void t_edge_row(const Row<VEC, G, R> &x, const Row<VE
     // live = 0: a padding repeat of the previous edge (odd count) adds nothing; keeping it
     // unconditional keeps its row load in flight with its partner's instead of behind a branch
     // (rsq + one Newton step, about half an ulp: the backward only needs the value to be accurate;
-    // the forward's selection uses IEEE sqrt / division on whole rows, agg_fwd_impl.h)
+    // the forward's selection uses IEEE sqrt / division on whole rows, agg_fwd_args.h)
     const float invj = inv_norm_of(group_sum<G>(x.dot_partial(x)));
     const float d = group_sum<G>(gp.dot_partial(x));
     fma_row<VEC, G, R>(acc, d * invj * live, x);

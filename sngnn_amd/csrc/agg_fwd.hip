@@ -1,6 +1,9 @@
-// C-ABI entries of the fused aggregation forward (see agg_fwd_impl.h for the kernels).
+// C-ABI entries of the fused aggregation forward (the kernels: agg_fwd_impl.h and the headers it lists; none is compiled here).
 #include <atomic>
-#include "agg_fwd_impl.h"
+#include "agg_fwd_args.h"
+#include "agg_fwd_filter.h"
+#include "fwd_plan.h"
+#include "head_row.h"
 #include "entry.h"
 
 using namespace sngnn;
@@ -427,7 +430,7 @@ extern "C" int sngnn_agg_forward_half(const sngnn_graph_t *g, const void *h, int
 extern "C" int64_t sngnn_agg_head_workspace_bytes(const sngnn_graph_t *g)
 {
     // one 16-byte entry per wave of the head role and per split row
-    return g ? ((int64_t)256 * 32 + g->n_split) * 16 + 256 : 0;
+    return g ? ((int64_t)HEAD_ROLE_WAVES_MAX + g->n_split) * 16 + 256 : 0;
 }
 
 extern "C" int sngnn_agg_head_supported(const sngnn_graph_t *g, int C, int top_k)

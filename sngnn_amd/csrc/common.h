@@ -8,17 +8,11 @@
 #include <vector>
 
 #include "sngnn_hip.h"
-#include "ws_layout.h"   // filter_row_bytes, CAND_MAX_K, the workspace layouts
+#include "ws_layout.h"   // row classes, ceil_div, filter_row_bytes, CAND_MAX_K, the workspace layouts
 
 namespace sngnn {
 
-// ---- row classes of the aggregation kernels (by in-degree) -----------------
-constexpr int SMALL_T = 16;    // deg <= SMALL_T : one G-lane group per row
-constexpr int WAVE_T = 128;    // deg <= WAVE_T  : one wave per row
-constexpr int CHUNK = 128;     // deg >  WAVE_T  : split into CHUNK-edge wave tasks
-constexpr int BLOCK = 256;     // threads per workgroup of the main kernels
-constexpr int WAVES = BLOCK / 64;
-constexpr int FIN_BLOCK = 1024;   // threads per workgroup of the split-row finalize
+// (the row classes by in-degree, the workgroup sizes and ceil_div: ws_layout.h - plain C++ that fwd_plan.h shares)
 constexpr float EPS_NORM = 1e-12f;   // F.normalize eps (models.py:122,238,325)
 
 void set_error(const std::string &msg);
@@ -50,8 +44,6 @@ int set_knn_route(int v);      // knn.hip (knob 6)
 int set_cosine_split(int v);   // toolbox.hip (knob 7)
 int set_hist_copies(int v);    // cosine_hist.hip (knob 10)
 bool fp32_mfma_only();         // knob 5 == 1: the fp32 contractions stay on fp32 MFMAs
-
-inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Lane layout of one node row for C channels:
 //   VEC floats per lane per step, G lanes per group, R steps  (C <= VEC*G*R).
@@ -117,7 +109,7 @@ struct sngnn_graph {
     float *inv_deg = nullptr;  // [N] 1 / max(in-degree, 1) by row (backward pass S)
     // backward, node-centric path: the small sources of sdesc / sperm are ordered [not fused |
     // fused], natural order inside each; fused = owned, in-degree and out-degree <= SMALL_T
-    // kept-bit layout the forward can write without atomics ("kbits": agg_fwd_impl.h, agg_bwd_impl.h):
+    // kept-bit layout the forward can write without atomics ("kbits": agg_fwd_args.h, agg_bwd_impl.h):
     //   words [0, kb_wbase): one HALFWORD per row id (bit t = edge t of a small row);
     //   [kb_wbase, kb_tbase): 4 words per wave row, by slot;  [kb_tbase, kb_words): 4 words per split-row task.
     // csc_bit[q] = the bit index of CSC entry q's edge in that layout (static); nullptr = layout unavailable

@@ -482,7 +482,7 @@ __device__ __forceinline__ bool norm_clamped(float sumsq) { return sumsq < EPS_N
 
 // cosine of target row a (inverse norm inv_i) and source row x from the UN-normalised rows:
 // <a, x> * (inv_i * inv_j).  Used by the backward and the attention mode, where the value
-// only has to be accurate; the selecting forward scores unit rows instead (agg_fwd_impl.h:
+// only has to be accurate; the selecting forward scores unit rows instead (agg_fwd_args.h:
 // normalise-then-dot, so that equal unit rows give equal bits).
 template <int VEC, int G, int R>
 __device__ __forceinline__ float edge_score(const Row<VEC, G, R> &a, float inv_i,

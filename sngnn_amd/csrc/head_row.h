@@ -2,7 +2,7 @@
 // four channels per lane) - log_softmax (models.py:86,211,303), the row's NLL term, its arg-max
 // against the label (train.py:81-84) and d loss / d logits.  One instruction sequence for the
 // stand-alone head kernel (head.hip: k_head_groups) and for the head inside the aggregation's second
-// launch (agg_fwd_impl.h: head_store_row): the same bits either way.
+// launch (agg_fwd_head.h: head_store_row): the same bits either way.
 #pragma once
 #include "common.h"
 

@@ -165,7 +165,7 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4v &a, const u32x4v &b, con
 // instead of 36 us; rocBLAS: 83 us)
 // NORM: the epilogue also writes F.normalize of the finished rows (models.py:237-238 are adjacent
 // lines) - unit rows, clamped norms and, when asked for, the fp16 filter rows - with the very
-// instruction sequence of k_normalize_rows (agg_fwd_impl.h): a finished 16-row tile goes through a
+// instruction sequence of k_normalize_rows (agg_fwd_roles.h): a finished 16-row tile goes through a
 // wave-private LDS tile into the aggregation's row layout (VEC 4, G = 8 or 16 lanes per row),
 // there the same fma chain, the same DPP tree, the same IEEE square root and division.  Needs
 // C % 4 == 0.  h itself then leaves from that layout too (16-byte stores).

@@ -18,7 +18,8 @@
 //   sngnn_replica_blend_*       the blend with beta[R]: forward, and backward with d beta[R], per replica
 //                               the grid and reduction tree of sngnn_blend_backward
 // Every sum is fixed-order: no float atomics.  Nothing here blocks the host.
-#include "agg_fwd_impl.h"
+#include "agg_fwd_filter.h"
+#include "agg_fwd_select.h"
 #include "entry.h"
 #include "head_row.h"
 
@@ -35,7 +36,7 @@ __device__ __forceinline__ float rep_wsum(float v)
 
 // ---------------------------------------------------------------------------
 // Unpack + bias + F.normalize: union row u = r N + i <- hs[i, r C .. r C + C) + bias[r].  The
-// lane layout, loop and normalisation are k_normalize_rows' (agg_fwd_impl.h), so n / nrm / filt are
+// lane layout, loop and normalisation are k_normalize_rows' (agg_fwd_roles.h), so n / nrm / filt are
 // the bits sngnn_normalize_rows_filter computes from the unpacked rows.
 // ---------------------------------------------------------------------------
 template <int VEC, int G, int R>

@@ -2,6 +2,7 @@
 // Plain C++ on plain counts (no HIP, no graph object): the size query (graph.hip) and every entry point that carves
 // the buffer (agg_fwd.hip, agg_bwd.hip, attn.hip, signed.hip) read the same offsets, and a host program can check
 // them (tests/test_workspace_layout_cpu.py).  All offsets and totals are BYTES from the start of the workspace.
+// Also here, because the forward's launch plan (fwd_plan.h) is plain C++ too: the row classes and workgroup sizes.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -10,7 +11,16 @@
 
 namespace sngnn {
 
-constexpr int CAND_MAX_K = 32;   // split rows: chunk-local candidates are kept for k <= this (agg_fwd_impl.h)
+// ---- row classes of the aggregation kernels (by in-degree) -----------------
+constexpr int SMALL_T = 16;    // deg <= SMALL_T : one G-lane group per row
+constexpr int WAVE_T = 128;    // deg <= WAVE_T  : one wave per row
+constexpr int CHUNK = 128;     // deg >  WAVE_T  : split into CHUNK-edge wave tasks
+constexpr int BLOCK = 256;     // threads per workgroup of the main kernels
+constexpr int WAVES = BLOCK / 64;
+constexpr int FIN_BLOCK = 1024;   // threads per workgroup of the split-row finalize
+constexpr int CAND_MAX_K = 32;   // split rows: chunk-local candidates are kept for k <= this (fwd_plan.h)
+
+inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 // bytes of `floats` fp32 values, rounded up to whole 16-byte vectors (what follows holds 16-byte aligned rows)
@@ -29,7 +39,7 @@ inline int64_t filter_row_bytes(int C)
 // forward (sngnn_agg_forward*): three 256-byte aligned tables in front of the split rows' scratch
 //   unit rows [Ntot][C] | norms [Ntot] | fp16 filter rows [Ntot][filter_row_bytes(C)] |
 //   scores of the split rows' edges | one partial row [C] per split task | CAND_MAX_K candidate keys per task |
-//   CAND_MAX_K candidate source ids per task | one done word per task (the finalize role: agg_fwd_impl.h)
+//   CAND_MAX_K candidate source ids per task | one done word per task (the finalize role: agg_fwd_fin.h)
 struct FwdLayout { int64_t unit, nrm, filt, scores, partial, cand_key, cand_src, fin_done, total; };
 
 inline FwdLayout fwd_layout(int64_t Ntot, int64_t split_edges, int64_t n_tasks, int C)
