@@ -678,6 +678,58 @@ int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out, const floa
                        const float *att_dst, int H, int C, float negative_slope, float *grad_xp, float *grad_att,
                        void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------
+ * ACM-GCN's low / high / identity filterbank with its three-way attention: csrc/acm.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * GraphConvolution2.forward for model_type 'acmgcn' (relu != 0) / 'acmsgc' (relu == 0), variant = False, after its
+ * three linear maps, P = X [W_low | W_high | W_mlp] = [Pl | Ph | Pm], dev f32 [N, 3C]:
+ *     L = adj_low Pl,  H = adj_high Ph,  M = Pm,  o* = relu(L | H | M),
+ *     d = (<ol, a_low>, <oh, a_high>, <om, a_mlp>),  att = softmax(sigmoid(d) att_vec / 3),
+ *     out = 3 (att_0 ol + att_1 oh + att_2 om)
+ * for the adjacency whose row i carries n_i entries (its diagonal among them) of weight 1 / n_i each, adj_high =
+ * I - adj_low: the graph holds adj_low's pattern (source = column, target = row; loops kept, none added; every row
+ * holds its diagonal; an unpartitioned graph, SNGNN_EINVAL otherwise), n_i is its rowptr's difference and no weight is
+ * read per entry:
+ *     L_i = S^l_i / n_i,  H_i = (1 - 1 / n_i) Ph_i - S^h_i / n_i,
+ *     S^l_i = sum over row i of Pl[col],  S^h_i = sum over the off-diagonal entries of row i of Ph[col]
+ * (the reference's own terms: Ph_i - Ph_i / n_i inside one sum would cancel what the reference never adds)
+ * - one column id and one contiguous 8C-byte slice of P per entry on the row classes of the other gather kernels
+ * (lane group up to 16 entries, one wave up to 128, 128-entry tasks + a finalize); fixed summation order, no
+ * floating-point atomics, no host synchronisation.  Limits: 1 <= C, 2C <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE
+ * otherwise).  Rows aligned to 4 * vec bytes (vec = 4, 2, 1 for C % 4 == 0, C % 2 == 0, odd C).
+ */
+/* bytes of device workspace of the two entries below: the split rows' task partials [tasks, 2C] of either side, the
+ * backward's scaled gradients [N, 2C] and the per-workgroup partials of the parameter gradients (f64); 0 outside
+ * the limits */
+int64_t sngnn_acm_workspace_bytes(const sngnn_graph_t *g, int C);
+/*
+ * Replaces: models.py:1787-1791 and 1809-1818 (1820-1830 with relu == 0) after the three mm - two spmm over COO
+ * entries of 20 bytes each, three relu, three [N, C] x [C, 1] products, cat, sigmoid, the 3x3 mm, softmax, three
+ * broadcasts and two adds, each an [N, C] or [N, 3] pass with its saved tensor: here one gather whose store
+ * epilogue does the rest.
+ *   a_low, a_high, a_mlp  dev f32 [C]     att_vec  dev f32 [3, 3]
+ *   out   dev f32 [N, C]
+ *   LH    dev f32 [N, 2C]   the pre-activations [L | H]   } all the backward needs saved next to P
+ *   datt  dev f32 [N, 6]    (d_0..2, att_0..2) per row    }
+ */
+int sngnn_acm_forward(const sngnn_graph_t *g, const float *P, const float *a_low, const float *a_high,
+                      const float *a_mlp, const float *att_vec, int C, int relu, float *out, float *LH, float *datt,
+                      void *workspace, void *stream);
+/*
+ * Replaces: autograd through the sequence above.  Pass A, row-local: grad_out through the mix, the softmax, the
+ * 3x3 product, the sigmoid, the three dots and relu' (the masks L > 0, H > 0, M > 0 of the stored fp32
+ * pre-activations) gives gL, gH, gM; pass B, the transpose gather-sum over the other side of the graph:
+ *     grad_P = [ sum_{i : j in row i} gL_i / n_i  |  (1 - 1 / n_j) gH_j - sum_{i != j : j in row i} gH_i / n_i  |  gM_j ]
+ *   grad_P       dev f32 [N, 3C]
+ *   grad_params  dev f64 [3C + 9]   grad a_low, a_high, a_mlp [C] each, then grad att_vec [3, 3] - per-workgroup
+ *                                   partials in double added by one reducer launch in a fixed order
+ */
+int sngnn_acm_backward(const sngnn_graph_t *g, const float *grad_out, const float *P, const float *LH,
+                       const float *datt, const float *a_low, const float *a_high, const float *a_mlp,
+                       const float *att_vec, int C, int relu, float *grad_P, double *grad_params, void *workspace,
+                       void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

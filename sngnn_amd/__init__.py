@@ -3,6 +3,7 @@ aggregation path behind the reference's own nn.Module API.
 
 The aggregation runs in hand-written HIP (libsngnn_hip.so, C ABI in
 include/sngnn_hip.h); there is no CPU fallback."""
+from .acmgcn import ACMGCN, GraphConvolution2
 from .conv import AGNNConv, SNConv, SNConv_plus, SNConv_plus_plus
 from .gatnet import GAT, GATConv
 from .ggcn import GGCN, GGCNlayer_SP
@@ -12,4 +13,4 @@ from .synth import Data
 
 __all__ = ["SNConv", "SNConv_plus", "SNConv_plus_plus", "SNGNN", "SNGNN_Plus",
            "SNGNN_Plus_Plus", "AGNNConv", "AGNN", "GGCNlayer_SP", "GGCN", "MLP", "GPR_prop",
-           "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "Data"]
+           "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "GraphConvolution2", "ACMGCN", "Data"]

@@ -95,6 +95,9 @@ SIGNATURES = {
     "sngnn_gat_workspace_bytes": (_i64, [_vp, _i32, _i32]), "sngnn_gat_scores": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_gat_forward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "sngnn_gat_backward": (_i32, [_vp] * 9 + [_i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "sngnn_acm_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_acm_forward": (_i32, [_vp] * 6 + [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "sngnn_acm_backward": (_i32, [_vp] * 9 + [_i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),

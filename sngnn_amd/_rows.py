@@ -13,7 +13,9 @@ from . import _lib
 HALF_DTYPES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
-def check_rows(t: torch.Tensor, n: int, what: str, half: bool = False) -> torch.Tensor:
+def check_rows(t: torch.Tensor, n: int, what: str, half: bool = False, max_channels: int = _lib.MAX_CHANNELS) -> torch.Tensor:
+    """``max_channels``: the widest row the operator takes where that is not the library's limit itself (the ACM
+    filterbank's [N, 3C] table: 2C <= MAX_CHANNELS)."""
     if t.dtype != torch.float32 and not (half and t.dtype in HALF_DTYPES):
         if half:
             raise ValueError(f"{what} must be float32, float16 or bfloat16, got {t.dtype}")
@@ -22,8 +24,8 @@ def check_rows(t: torch.Tensor, n: int, what: str, half: bool = False) -> torch.
         raise ValueError(f"{what} must live on the GPU (there is no CPU path)")
     if t.dim() != 2 or t.size(0) != n:
         raise ValueError(f"{what} must have shape [{n}, C], got {tuple(t.shape)}")
-    if not 1 <= t.size(1) <= _lib.MAX_CHANNELS:
-        raise ValueError(f"{what}: C must be in [1, {_lib.MAX_CHANNELS}]")
+    if not 1 <= t.size(1) <= max_channels:
+        raise ValueError(f"{what}: C must be in [1, {max_channels}]")
     return t.contiguous()
 
 

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._rows import HALF_DTYPES, check_flat as _check_flat, check_grad_dtype as _check_grad_dtype, check_rows as _check_rows
+from .acm import acm_filterbank, acm_filterbank_fused, acm_filterbank_plain  # noqa: F401  (csrc/acm.hip)
 from .batchnorm import _BatchNormAct, batch_norm_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
 from .gat import gat_propagate  # noqa: F401  (csrc/gat.hip)
 from .graph import Graph
