@@ -110,10 +110,37 @@ int64_t sngnn_graph_workspace_bytes(const sngnn_graph_t *g, int C);
  *          3 cscptr   int32 [N_total+1]  CSC by source
  *          4 csc_eid  int32 [E']    CSR edge index of each CSC entry
  *          5 rperm    int32 [N]     rows sorted by in-degree, descending (stable)
+ *          6 csc_dst  int32 [E']    local target row of each CSC entry
+ *          7 csc_pos  int32 [E']    CSC position of each CSR edge (inverse of csc_eid)
+ *          8 sperm    int32 [N_total]  sources by out-degree class, descending (stable): out-degree above 16,
+ *                                   then the small sources that are not fused, then the fused nodes
+ *          9 rdesc    int4  [N]     per slot of rperm: {row, first CSR edge, in-degree, first entry in col_s}
+ *         10 col_s    int32 [E']    col with the rows in rperm's slot order
+ *         11 rperm_b  int32 [N]     rows by in-degree above 16, else by bucket of 4 degrees; descending (stable)
+ *         12 rdesc_b  int4  [N]     rdesc of that order (.w: first entry in col_s_b)
+ *         13 col_s_b  int32 [E']    col with the rows in rperm_b's slot order
+ *         14 sdesc    int4  [N_total]  per slot of sperm: {source, first CSC entry, out-degree, 0}
+ *         15 fdesc    int4  [fused nodes]  natural order: {node, first CSR edge, first CSC entry,
+ *                                   in-degree | out-degree << 8}
+ *         16 trest    int4  [..]    owned rows with in-degree <= 16 and out-degree > 16, natural order:
+ *                                   {row, first CSR edge, in-degree, 0}
+ *         17 task_slot, 18 task_chunk  int32 [tasks]  one task per 128 edges of a row with in-degree > 128
+ *                                   (slot of rperm, chunk inside the row), in slot order
+ *         19 task_order int32 [tasks]  the order in which the forward deals those tasks (a permutation)
+ *         20 split_soff, 21 split_task0  int32 [split rows + 1]  running edge / task counts of those rows
+ *         22 stask_slot, 23 stask_chunk  int32 [source tasks]  the same for sources with out-degree > 128
+ *         24 ssplit_task0  int32 [split sources + 1]
+ *         25 csc_bit  int32 [E']    bit index of each CSC entry's edge in the kept-bit layout; length 0
+ *                                   where the layout was not built (a partition, a graph without edges)
+ *         26 inv_deg  float [N]     1 / max(in-degree, 1)
+ * Ids 11..13 have length 0 for a graph without owned rows.
  */
 int sngnn_graph_copy_array(const sngnn_graph_t *g, int which, void *host_dst);
 /* device pointer to the same arrays (owned by the graph) */
 const void *sngnn_graph_array_dev(const sngnn_graph_t *g, int which);
+/* length of array `which` in 4-byte elements (an int4 descriptor counts as four); 0 for an array that
+ * was not built, -1 for an unknown id */
+int64_t sngnn_graph_array_len(const sngnn_graph_t *g, int which);
 
 /* ------------------------------------------------------------------------
  * Fused aggregation:  F.normalize + per-edge cosine + top-k/threshold

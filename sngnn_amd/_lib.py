@@ -38,6 +38,7 @@ SIGNATURES = {
     "sngnn_graph_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_graph_copy_array": (_i32, [_vp, _i32, _vp]),
     "sngnn_graph_array_dev": (_vp, [_vp, _i32]),
+    "sngnn_graph_array_len": (_i64, [_vp, _i32]),
     "sngnn_agg_forward": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_normalize_rows": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "sngnn_filter_row_bytes": (_i64, [_i32]),

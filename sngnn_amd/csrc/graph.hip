@@ -595,34 +595,67 @@ int64_t sngnn_graph_workspace_bytes(const sngnn_graph_t *g, int C)
     return sngnn::graph_workspace_bytes(g->N, g->Ntot, g->Ep, g->n_tasks, g->n_stasks, g->split_edges, C);
 }
 
-static const void *graph_array(const sngnn_graph_t *g, int which, int64_t *n)
+// the one table of the structure arrays: pointer and length in 4-byte elements (an int4 descriptor counts
+// as four); -1 = unknown id.  An array that was not built (csc_bit of a partition, the streaming order of a
+// graph without rows) has length 0 and may be nullptr.
+static int64_t graph_array(const sngnn_graph_t *g, int which, const void **p)
 {
+    const int64_t n_fwd_b = g->rperm_b ? g->N : 0;
     switch (which) {
-    case 0: *n = g->N + 1; return g->rowptr;
-    case 1: *n = g->Ep; return g->col;
-    case 2: *n = g->Ep; return g->eid;
-    case 3: *n = g->Ntot + 1; return g->cscptr;
-    case 4: *n = g->Ep; return g->csc_eid;
-    case 5: *n = g->N; return g->rperm;
-    default: *n = 0; return nullptr;
+    case 0: *p = g->rowptr; return g->N + 1;
+    case 1: *p = g->col; return g->Ep;
+    case 2: *p = g->eid; return g->Ep;
+    case 3: *p = g->cscptr; return g->Ntot + 1;
+    case 4: *p = g->csc_eid; return g->Ep;
+    case 5: *p = g->rperm; return g->N;
+    case 6: *p = g->csc_dst; return g->Ep;
+    case 7: *p = g->csc_pos; return g->Ep;
+    case 8: *p = g->sperm; return g->Ntot;
+    case 9: *p = g->rdesc; return 4 * g->N;
+    case 10: *p = g->col_s; return g->Ep;
+    case 11: *p = g->rperm_b; return n_fwd_b;
+    case 12: *p = g->rdesc_b; return 4 * n_fwd_b;
+    case 13: *p = g->col_s_b; return g->col_s_b ? g->Ep : 0;
+    case 14: *p = g->sdesc; return 4 * g->Ntot;
+    case 15: *p = g->fdesc; return 4 * (int64_t)g->n_fused;
+    case 16: *p = g->trest; return 4 * (int64_t)g->n_trest;
+    case 17: *p = g->task_slot; return g->n_tasks;
+    case 18: *p = g->task_chunk; return g->n_tasks;
+    case 19: *p = g->task_order; return g->n_tasks;
+    case 20: *p = g->split_soff; return g->n_split + 1;
+    case 21: *p = g->split_task0; return g->n_split + 1;
+    case 22: *p = g->stask_slot; return g->n_stasks;
+    case 23: *p = g->stask_chunk; return g->n_stasks;
+    case 24: *p = g->ssplit_task0; return g->n_ssplit + 1;
+    case 25: *p = g->csc_bit; return g->csc_bit ? g->Ep : 0;
+    case 26: *p = g->inv_deg; return g->N;
+    default: *p = nullptr; return -1;
     }
+}
+
+int64_t sngnn_graph_array_len(const sngnn_graph_t *g, int which)
+{
+    if (!g) return -1;
+    const void *p = nullptr;
+    return graph_array(g, which, &p);
 }
 
 int sngnn_graph_copy_array(const sngnn_graph_t *g, int which, void *host_dst)
 {
     SN_REQUIRE(g && host_dst, SNGNN_EINVAL, "NULL argument");
-    int64_t n = 0;
-    const void *p = graph_array(g, which, &n);
-    SN_REQUIRE(p != nullptr, SNGNN_EINVAL, "unknown array id");
-    if (n > 0) SN_HIP(hipMemcpy(host_dst, p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    const void *p = nullptr;
+    const int64_t n = graph_array(g, which, &p);
+    SN_REQUIRE(n >= 0, SNGNN_EINVAL, "unknown array id");
+    if (n > 0 && p) SN_HIP(hipMemcpy(host_dst, p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return SNGNN_OK;
 }
 
 const void *sngnn_graph_array_dev(const sngnn_graph_t *g, int which)
 {
     if (!g) return nullptr;
-    int64_t n = 0;
-    return graph_array(g, which, &n);
+    const void *p = nullptr;
+    (void)graph_array(g, which, &p);
+    return p;
 }
 
 }  // extern "C"

@@ -15,7 +15,12 @@ import torch
 
 from . import _lib
 
-_ARRAYS = {"rowptr": 0, "col": 1, "eid": 2, "cscptr": 3, "csc_eid": 4, "rperm": 5}
+_ARRAYS = {"rowptr": 0, "col": 1, "eid": 2, "cscptr": 3, "csc_eid": 4, "rperm": 5,
+           "csc_dst": 6, "csc_pos": 7, "sperm": 8, "rdesc": 9, "col_s": 10, "rperm_b": 11, "rdesc_b": 12,
+           "col_s_b": 13, "sdesc": 14, "fdesc": 15, "trest": 16, "task_slot": 17, "task_chunk": 18,
+           "task_order": 19, "split_soff": 20, "split_task0": 21, "stask_slot": 22, "stask_chunk": 23,
+           "ssplit_task0": 24, "csc_bit": 25, "inv_deg": 26}
+_DESCRIPTORS = ("rdesc", "rdesc_b", "sdesc", "fdesc", "trest")          # int4 per entry
 
 LOOPS_REPLACE = _lib.LOOPS_REPLACE
 
@@ -93,15 +98,19 @@ class Graph:
         return self.cached("csr_entries", _csr_entries)
 
     def array(self, name: str) -> np.ndarray:
-        """Host copy of one of the structure arrays (tests / inspection)."""
+        """Host copy of one of the structure arrays (tests / inspection): int32, ``[-1, 4]`` for the descriptor
+        arrays, float32 for ``inv_deg``; empty for an array the build left out (``csc_bit`` of a partition)."""
         which = _ARRAYS[name]
-        n = {0: self.num_nodes + 1, 3: self.num_total_nodes + 1,
-             5: self.num_nodes}.get(which, self.num_edges)
-        out = np.empty(n, dtype=np.int32)
+        lib = _lib.load()
+        n = int(lib.sngnn_graph_array_len(self._h, which))
+        if n < 0:
+            raise ValueError(f"the library knows no array {name!r} (id {which})")
+        out = np.empty(max(n, 1), dtype=np.int32)[:n]       # (never a NULL destination)
         # (not through _lib.call: a blocking copy to host memory, the entry takes no stream)
-        _lib.check(_lib.load().sngnn_graph_copy_array(self._h, which, out.ctypes.data),
-                   "sngnn_graph_copy_array")
-        return out
+        _lib.check(lib.sngnn_graph_copy_array(self._h, which, out.ctypes.data), "sngnn_graph_copy_array")
+        if name in _DESCRIPTORS:
+            return out.reshape(-1, 4)
+        return out.view(np.float32) if name == "inv_deg" else out
 
     def __del__(self):
         h = getattr(self, "_h", None)

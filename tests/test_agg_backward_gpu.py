@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import sngnn_oracle as O
-from tests import arbiter
+from tests import arbiter, graph_ref
 from tests.helpers import assert_close, oracle_fixed_mask, random_graph
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +95,7 @@ def test_eps_clamped_rows(cuda):
     for ei_c, nc, hc, gc in ((ei, n, h, gout), (big, n2, h2, gout2)):
         for rem in (False, True):
             gr = Graph(ei_c.to(cuda), nc, True, rem)
+            graph_ref.assert_csr(gr, ei_c, nc, True, rem)          # the arbiter is fed the graph's own CSR
             rowptr, col = gr.array("rowptr"), gr.array("col")
             if nc == n2:
                 deg = np.diff(rowptr)
@@ -275,6 +276,7 @@ def test_node_centric_backward_equals_the_two_passes(cuda, n, e, C, hubs, rem, k
 
     try:
         g = Graph(ei, n, True, rem)
+        graph_ref.assert_csr(g, ei, n, True, rem)          # the arbiter is fed the graph's own CSR
         _, wsel, *_ = ops.aggregate_forward(g, h, k, thr, save_for_backward=True)
         mag = arbiter.aggregate(g.array("rowptr"), g.array("col"), (wsel > -3.0).cpu(), h.cpu(), gout.cpu())["MAG_grad"]
         two = _backward_in_mode(lib, 1, g, h, gout, wsel, None)

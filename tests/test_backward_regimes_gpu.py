@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from oracle import sngnn_oracle as O
-from tests import arbiter, helpers
+from tests import arbiter, graph_ref, helpers
 from tests.helpers import REGIMES, oracle_fixed_mask, regime_edges, regime_inputs, row_classes
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +38,12 @@ class World:
         self.graphs = {"loops removed": Graph(ei, N, True, True), "loops kept": Graph(ei, N, True, False),
                        f"partition [{lo}, {hi})": Graph(ei, N, True, True, row_range=(lo, hi))}
         self.attn = Graph(ei, N, True, LOOPS_REPLACE)
-        self.csr = {id(g): (g.array("rowptr").astype(np.int64), g.array("col").astype(np.int64))
+        # the arbiter below is fed the graphs' own CSR: first it must BE the edge list's (tests/graph_ref.py)
+        graph_ref.assert_csr(self.graphs["loops removed"], self.ei, N, True, 1)
+        graph_ref.assert_csr(self.graphs["loops kept"], self.ei, N, True, 0)
+        graph_ref.assert_csr(self.graphs[f"partition [{lo}, {hi})"], self.ei, N, True, 1, row_range=(lo, hi))
+        graph_ref.assert_csr(self.attn, self.ei, N, True, LOOPS_REPLACE)
+        self.csr ={id(g): (g.array("rowptr").astype(np.int64), g.array("col").astype(np.int64))
                     for g in list(self.graphs.values()) + [self.attn]}
         for name, g in self.graphs.items():
             deg = np.diff(self.csr[id(g)][0])

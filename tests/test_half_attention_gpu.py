@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from oracle import sngnn_oracle as O
 from sngnn_amd import ops, synth
 from sngnn_amd.graph import LOOPS_REPLACE, Graph
-from tests import arbiter
+from tests import arbiter, graph_ref
 from tests.helpers import REGIMES, oracle_signed_fixed, random_graph, regime_inputs
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +50,9 @@ class World:
         self.ei = torch.unique(torch.cat([ei, torch.tensor(extra).t()], dim=1), dim=1)
         self.attn = Graph(self.ei.to(cuda), n, True, LOOPS_REPLACE)
         self.signed = Graph(self.ei.to(cuda), n, False, True)
+        # test_against_the_arbiter_bf16 feeds the arbiter these graphs' own CSR: it must BE the edge list's
+        graph_ref.assert_csr(self.attn, self.ei, n, True, LOOPS_REPLACE)
+        graph_ref.assert_csr(self.signed, self.ei, n, False, 1)
         for g in (self.attn, self.signed):
             deg = np.diff(g.array("rowptr").astype(np.int64))
             tasks = -(-deg[deg > 128] // 128)                 # 128-edge tasks per split row

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import arbiter, helpers
+from tests import arbiter, graph_ref, helpers
 from tests.helpers import (REGIMES, SIGNED_REGIMES, oracle_signed_fixed, oracle_weighted, regime_edges, row_classes,
                            signed_inputs)
 
@@ -41,6 +41,10 @@ class World:
         full = helpers.adj_with_diagonal(regime_edges(N), N)
         adj = torch.sparse_coo_tensor(torch.stack([full[1], full[0]]), torch.ones(full.size(1)), (N, N)).coalesce()
         self.full, _, self.full_aux = _AdjStructure(adj.to(cuda)).full()         # the layer's own: diagonal kept
+        # the arbiter below is fed the graphs' own CSR: first it must BE the edge list's (tests/graph_ref.py)
+        graph_ref.assert_csr(self.graphs["whole"], ei, N, False, 1)
+        graph_ref.assert_csr(self.graphs[f"partition [{lo}, {hi})"], ei, N, False, 1, row_range=(lo, hi))
+        graph_ref.assert_csr(self.full, torch.stack([adj._indices()[1], adj._indices()[0]]), N, False, 0)
         self.csr = {id(g): (g.array("rowptr").astype(np.int64), g.array("col").astype(np.int64))
                     for g in list(self.graphs.values()) + [self.full]}
         for name, g in self.graphs.items():
