@@ -563,6 +563,26 @@ int sngnn_bn_train_backward(const float *grad_out, const float *x, const float *
                             const float *gamma, const float *save_mean, const float *save_invstd,
                             const unsigned char *keep, float keep_scale, const void *seed, float p, float *grad_x,
                             float *grad_gamma, float *grad_beta, float *grad_bias, void *workspace, void *stream);
+/*
+ * The other order, norm -> relu -> dropout: what GCNII runs behind every GCN2Conv in TRAINING (models.py:1296-1298 and
+ * the next layer's dropout, :1295): `self.bns[i](x)` on the batch's statistics, `x.relu()`, `F.dropout(x)`.
+ *   mean_c = sum_i x / N,  var_c = sum_i (x - mean)^2 / N (biased),  invstd = 1 / sqrt(var + eps),
+ *   xhat = (x - mean) * invstd,  y = xhat * gamma + beta,  out = max(y, 0) * keep * keep_scale
+ * The same three launches each way, the same double / Chan summation, running statistics, keep / seed and workspace
+ * (sngnn_bn_train_workspace_bytes) as the pair above; there is no conv bias.  Nothing of size [N, C] is saved: the
+ * backward recomputes xhat, the relu mask [xhat * gamma + beta > 0] and the keep mask from x.  With
+ * gy = grad_out * keep * keep_scale * [y > 0]:  grad_beta = sum_i gy,  grad_gamma = sum_i gy xhat,
+ *   grad_x = invstd * (gamma gy - gamma grad_beta / N - xhat gamma grad_gamma / N).
+ * The same argument errors as above.
+ */
+int sngnn_bn_post_forward(const float *x, int64_t N, int C, const float *gamma, const float *beta, double eps,
+                          double momentum, float *running_mean, float *running_var, const unsigned char *keep,
+                          float keep_scale, const void *seed, float p, float *out, float *save_mean,
+                          float *save_invstd, void *workspace, void *stream);
+int sngnn_bn_post_backward(const float *grad_out, const float *x, int64_t N, int C, const float *gamma,
+                           const float *beta, const float *save_mean, const float *save_invstd,
+                           const unsigned char *keep, float keep_scale, const void *seed, float p, float *grad_x,
+                           float *grad_gamma, float *grad_beta, void *workspace, void *stream);
 
 /*
  * The same two gather-sums on any graph, node-range partitions included (multi-GPU
@@ -756,6 +776,39 @@ int sngnn_acm_backward(const sngnn_graph_t *g, const float *grad_out, const floa
                        const float *datt, const float *a_low, const float *a_high, const float *a_mlp,
                        const float *att_vec, int C, int relu, float *grad_P, double *grad_params, void *workspace,
                        void *stream);
+
+/* ------------------------------------------------------------------------
+ * GCNII's layer, PyG 2.0.4's GCN2Conv (initial residual + identity mapping): csrc/gcn2.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * GCN2Conv.forward with shared weights on the adjacency of sngnn_prop_* (A^ of gcn_norm: the unpartitioned graph
+ * built with add_loops = 1, remove_loops = SNGNN_LOOPS_REPLACE; SNGNN_EINVAL otherwise):
+ *     s = (1 - alpha) (A^ x) + alpha x0,     out = (1 - beta) s + beta (s W)
+ * as two launches.  The scalars arrive as the fp32 values torch multiplies an fp32 tensor with.
+ *
+ * sngnn_gcn2_hop: s_i = a (dinv_i S_i) + b x0_i with S_i = sum_{e -> i} dinv_src x_src - the UNSCALED rows of x are
+ * gathered and each is multiplied by dinv[src], loaded next to the column id (4 more bytes per edge instead of a
+ * scaled copy of x per layer) - on the row classes of the other gather kernels (lane group, wave, 128-edge tasks +
+ * a finalize; fixed summation order, no atomics); every product and sum rounded separately.  x0 NULL: no b x0 term
+ * (alpha == 0, and the backward).  transpose != 0 walks the out-edges: a (A^T x), the backward's hop.
+ *   x, x0, out  dev f32 [N, C]   rows aligned to 4 * vec bytes (vec = 4, 2, 1 for C % 4 == 0, C % 2 == 0, odd C)
+ *   dinv        dev f32 [N]      sngnn_prop_dinv's output
+ *   workspace   sngnn_gcn2_workspace_bytes(g, C): the split rows' task partials of either side
+ *
+ * sngnn_gcn2_map: out = c0 s + c1 (s W), W dev f32 [C, C] row-major ([in, out]; transpose_w != 0: s W^T, the
+ * backward's g_s = (1 - beta) g + beta (g W^T)), 1 <= C <= SNGNN_GCN2_MAX_C (SNGNN_ERANGE otherwise).  s is
+ * streamed once in 32-row tiles with W resident in LDS; a dot product is four interleaved fp32 fma chains added
+ * pairwise.  rm != NULL (with invstd, gamma, beta_bn, all dev f32 [C]) adds the evaluation epilogue of the norm
+ * and relu behind the layer: out = max(((out - rm) * invstd) * gamma + beta_bn, 0), each step rounded.
+ * Both only enqueue.
+ */
+#define SNGNN_GCN2_MAX_C 128
+int64_t sngnn_gcn2_workspace_bytes(const sngnn_graph_t *g, int C);
+int sngnn_gcn2_hop(const sngnn_graph_t *g, const float *x, const float *x0, const float *dinv, float a, float b,
+                   int C, int transpose, float *out, void *workspace, void *stream);
+int sngnn_gcn2_map(const float *s, const float *w, float c0, float c1, int64_t N, int C, int transpose_w,
+                   const float *rm, const float *invstd, const float *gamma, const float *beta_bn, float *out,
+                   void *stream);
 
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward

@@ -81,6 +81,8 @@ SIGNATURES = {
     "sngnn_bn_train_workspace_bytes": (_i64, [_i32]),
     "sngnn_bn_train_forward": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _f32, _vp, _f32] + [_vp] * 5),
     "sngnn_bn_train_backward": (_i32, [_vp, _vp, _vp, _i64, _i32] + [_vp] * 4 + [_f32, _vp, _f32] + [_vp] * 6),
+    "sngnn_bn_post_forward": (_i32, [_vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _f32, _vp, _f32] + [_vp] * 5),
+    "sngnn_bn_post_backward": (_i32, [_vp, _vp, _i64, _i32] + [_vp] * 5 + [_f32, _vp, _f32] + [_vp] * 5),
     "sngnn_knn_workspace_bytes": (_i64, [_i64, _i32]),
     "sngnn_knn_graph": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -99,6 +101,9 @@ SIGNATURES = {
     "sngnn_acm_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_acm_forward": (_i32, [_vp] * 6 + [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_acm_backward": (_i32, [_vp] * 9 + [_i32, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_gcn2_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_gcn2_hop": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
+    "sngnn_gcn2_map": (_i32, [_vp, _vp, _f32, _f32, _i64, _i32, _i32] + [_vp] * 6),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),

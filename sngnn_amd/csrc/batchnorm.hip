@@ -115,9 +115,10 @@ __device__ __forceinline__ int bn_pow2(int RB) { int p = 1; while (p < RB) p <<=
 
 // ---- forward 1: (count, mean, M2) of r per workgroup and channel --------------------------------------------------
 // part: double [3][gridDim.x][C]
-template <int V>
-__global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float *__restrict__ x, const float *__restrict__ bias,
-                                                         int64_t N, int C, int G, int GW, int RB, double *__restrict__ part)
+// RELU: the statistics of r = max(x + bias, 0) (the bias -> relu -> norm order); otherwise of x itself (norm -> relu)
+template <int V, bool RELU>
+__device__ __forceinline__ void bn_stats_rows(const float *__restrict__ x, const float *__restrict__ bias, int64_t N, int C,
+                                              int G, int GW, int RB, double *__restrict__ part)
 {
     __shared__ double sn[BN_THREADS], sm[BN_THREADS][V], sq[BN_THREADS][V];
     const BnThread t = bn_thread<V>(G, GW, RB);
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float *__restrict
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float z = v[j] + b[j];
-                const double r = z > 0.f ? z : 0.f;
+                const double r = (!RELU || z > 0.f) ? z : 0.f;
                 if (cnt == 0.0) K[j] = r;
                 const double d = r - K[j];
                 s1[j] += d;
@@ -181,6 +182,20 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float *__restrict
             part[2 * plane + at + j] = sq[threadIdx.x][j];
         }
     }
+}
+
+template <int V>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_stats(const float *__restrict__ x, const float *__restrict__ bias,
+                                                         int64_t N, int C, int G, int GW, int RB, double *__restrict__ part)
+{
+    bn_stats_rows<V, true>(x, bias, N, C, G, GW, RB, part);
+}
+
+template <int V>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_post_stats(const float *__restrict__ x, int64_t N, int C, int G, int GW,
+                                                              int RB, double *__restrict__ part)
+{
+    bn_stats_rows<V, false>(x, nullptr, N, C, G, GW, RB, part);
 }
 
 // ---- forward 2: the channel's statistics from its nb partials; a workgroup per channel -----------------------------
@@ -427,6 +442,123 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_bwd_apply(const float *__rest
     }
 }
 
+// ---- the other order: norm -> relu -> dropout (GCNII, models.py:1295-1298).  The statistics are those of x itself
+// (k_bn_post_stats + k_bn_reduce_stats); y = xhat gamma + beta, out = max(y, 0) keep scale; the backward recomputes
+// xhat, the relu mask [y > 0] and keep from x: gy = g keep scale [y > 0], then the sums and grad_x of the first order
+// without its [z > 0] factor (k_bn_reduce_sums<2> between the two launches) ----------------------------------------
+template <int V, int KEEP>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_post_apply(const float *__restrict__ x, int64_t N, int C, int G, int GW,
+                                                              int RB, const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, const float *__restrict__ mean,
+                                                              const float *__restrict__ invstd,
+                                                              const unsigned char *__restrict__ keep,
+                                                              const unsigned long long *__restrict__ seedp, float p, float scale,
+                                                              float *__restrict__ out)
+{
+    const BnThread t = bn_thread<V>(G, GW, RB);
+    if (!t.active) return;
+    float ga[V], be[V], mu[V], is[V];
+    bn_chan<V>(gamma, t.c0, 1.f, ga);
+    bn_chan<V>(beta, t.c0, 0.f, be);
+    bn_chan<V>(mean, t.c0, 0.f, mu);
+    bn_chan<V>(invstd, t.c0, 1.f, is);
+    unsigned long long seed = 0;
+    if constexpr (KEEP == BN_SEED) seed = *seedp;
+    const int64_t step = (int64_t)gridDim.x * RB;
+#pragma unroll 2
+    for (int64_t row = (int64_t)blockIdx.x * RB + t.rr; row < N; row += step) {
+        const int64_t i = row * C + t.c0;
+        float v[V], o[V];
+        bool k[V];
+        bn_load<V>(x, i, v);
+        bn_keep<V, KEEP>(keep, seed, p, i, k);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float xh = (v[j] - mu[j]) * is[j];
+            float y = xh * ga[j] + be[j];
+            y = y > 0.f ? y : 0.f;
+            if constexpr (KEEP != BN_NONE) y = k[j] ? y * scale : 0.f;
+            o[j] = y;
+        }
+        bn_store<V>(out, i, o);
+    }
+}
+
+// FINAL = false: sum gy and sum gy * xhat per workgroup and channel, part: double [2][gridDim.x][C];
+// FINAL = true: grad_x = invstd * (gamma gy - m1 - xhat m2)
+template <int V, int KEEP, bool FINAL>
+__global__ __launch_bounds__(BN_THREADS) void k_bn_post_bwd(const float *__restrict__ g, const float *__restrict__ x, int64_t N,
+                                                            int C, int G, int GW, int RB, const float *__restrict__ gamma,
+                                                            const float *__restrict__ beta, const float *__restrict__ mean,
+                                                            const float *__restrict__ invstd, const float *__restrict__ m12,
+                                                            const unsigned char *__restrict__ keep,
+                                                            const unsigned long long *__restrict__ seedp, float p, float scale,
+                                                            float *__restrict__ gx, double *__restrict__ part)
+{
+    __shared__ double s0[FINAL ? 1 : BN_THREADS][V], s1[FINAL ? 1 : BN_THREADS][V];
+    const BnThread t = bn_thread<V>(G, GW, RB);
+    double a0[V], a1[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) a0[j] = a1[j] = 0.0;
+    if (t.active) {
+        float ga[V], be[V], mu[V], is[V], m1[V], m2[V];
+        bn_chan<V>(gamma, t.c0, 1.f, ga);
+        bn_chan<V>(beta, t.c0, 0.f, be);
+        bn_chan<V>(mean, t.c0, 0.f, mu);
+        bn_chan<V>(invstd, t.c0, 1.f, is);
+        bn_chan<V>(FINAL ? m12 : nullptr, t.c0, 0.f, m1);
+        bn_chan<V>(FINAL ? m12 + C : nullptr, t.c0, 0.f, m2);
+        unsigned long long seed = 0;
+        if constexpr (KEEP == BN_SEED) seed = *seedp;
+        const int64_t step = (int64_t)gridDim.x * RB;
+#pragma unroll 2
+        for (int64_t row = (int64_t)blockIdx.x * RB + t.rr; row < N; row += step) {
+            const int64_t i = row * C + t.c0;
+            float v[V], d[V], o[V];
+            bool k[V];
+            bn_load<V>(x, i, v);
+            bn_load<V>(g, i, d);
+            bn_keep<V, KEEP>(keep, seed, p, i, k);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const float xh = (v[j] - mu[j]) * is[j];
+                const float y = xh * ga[j] + be[j];
+                float gy = d[j];
+                if constexpr (KEEP != BN_NONE) gy = k[j] ? gy * scale : 0.f;
+                gy = y > 0.f ? gy : 0.f;
+                if constexpr (FINAL) {
+                    float u = ga[j] * gy;
+                    u = u - m1[j];
+                    u = u - xh * m2[j];
+                    o[j] = is[j] * u;
+                } else {
+                    a0[j] += (double)gy;
+                    a1[j] += (double)gy * (double)xh;
+                }
+            }
+            if constexpr (FINAL) bn_store<V>(gx, i, o);
+        }
+    }
+    if constexpr (!FINAL) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) { s0[threadIdx.x][j] = a0[j]; s1[threadIdx.x][j] = a1[j]; }
+        __syncthreads();
+        for (int m = bn_pow2(RB) >> 1; m >= 1; m >>= 1) {
+            if (t.active && t.rr < m && t.rr + m < RB) {
+                const int o = threadIdx.x + m * GW;
+#pragma unroll
+                for (int j = 0; j < V; ++j) { s0[threadIdx.x][j] += s0[o][j]; s1[threadIdx.x][j] += s1[o][j]; }
+            }
+            __syncthreads();
+        }
+        if (t.active && t.rr == 0) {
+            const int64_t plane = (int64_t)gridDim.x * C, at = (int64_t)blockIdx.x * C + t.c0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) { part[at + j] = s0[threadIdx.x][j]; part[plane + at + j] = s1[threadIdx.x][j]; }
+        }
+    }
+}
+
 // float4 / uchar4 accesses: C % 4 == 0 and every [N, C] base on a 16-byte boundary (a u8 mask then sits on 4 at least)
 static int bn_vec(int C, std::initializer_list<const void *> ps)
 {
@@ -537,6 +669,65 @@ extern "C" int sngnn_bn_train_backward(const float *grad_out, const float *x, co
                                                                 save_invstd, m12, keep, sd, p, keep_scale, grad_x, nullptr));
 #undef BN_K
     }
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+extern "C" int sngnn_bn_post_forward(const float *x, int64_t N, int C, const float *gamma, const float *beta, double eps,
+                                     double momentum, float *running_mean, float *running_var, const unsigned char *keep,
+                                     float keep_scale, const void *seed, float p, float *out, float *save_mean,
+                                     float *save_invstd, void *workspace, void *stream)
+{
+    if (int rc = bn_check_common(x, N, C, p, keep, seed)) return rc;
+    SN_REQUIRE(gamma && beta && out && save_mean && save_invstd && workspace, SNGNN_EINVAL, "NULL argument");
+    SN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), SNGNN_EINVAL,
+               "running_mean and running_var go together (both NULL: no running statistics)");
+    SN_REQUIRE(eps >= 0.0, SNGNN_EINVAL, "negative eps");
+    hipStream_t st = (hipStream_t)stream;
+    const int mode = bn_keep_mode(keep, seed, p);
+    if (mode == BN_NONE) keep_scale = 1.f;
+    const int V = bn_vec(C, {x, out, keep});
+    const BnGeom q = bn_geom(N, C, V);
+    const dim3 grid(q.nbx, q.slabs);
+    double *part = (double *)workspace;
+    if (V == 4) k_bn_post_stats<4><<<grid, BN_THREADS, 0, st>>>(x, N, C, q.G, q.GW, q.RB, part);
+    else k_bn_post_stats<1><<<grid, BN_THREADS, 0, st>>>(x, N, C, q.G, q.GW, q.RB, part);
+    k_bn_reduce_stats<<<C, BN_THREADS, 0, st>>>(part, q.nbx, C, N, eps, momentum, running_mean, running_var, save_mean,
+                                                save_invstd);
+#define BN_K(V_, M_) k_bn_post_apply<V_, M_>
+    BN_DISPATCH(V, mode, BN_K, <<<grid, BN_THREADS, 0, st>>>(x, N, C, q.G, q.GW, q.RB, gamma, beta, save_mean, save_invstd, keep,
+                                                            (const unsigned long long *)seed, p, keep_scale, out));
+#undef BN_K
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+extern "C" int sngnn_bn_post_backward(const float *grad_out, const float *x, int64_t N, int C, const float *gamma,
+                                      const float *beta, const float *save_mean, const float *save_invstd,
+                                      const unsigned char *keep, float keep_scale, const void *seed, float p, float *grad_x,
+                                      float *grad_gamma, float *grad_beta, void *workspace, void *stream)
+{
+    if (int rc = bn_check_common(x, N, C, p, keep, seed)) return rc;
+    SN_REQUIRE(grad_out && gamma && beta && save_mean && save_invstd && grad_x && grad_gamma && grad_beta && workspace,
+               SNGNN_EINVAL, "NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int mode = bn_keep_mode(keep, seed, p);
+    if (mode == BN_NONE) keep_scale = 1.f;
+    const int V = bn_vec(C, {grad_out, x, grad_x, keep});
+    const BnGeom q = bn_geom(N, C, V);
+    const dim3 grid(q.nbx, q.slabs);
+    double *part = (double *)workspace;
+    float *m12 = (float *)(part + bn_partial_doubles(C));
+    const unsigned long long *sd = (const unsigned long long *)seed;
+#define BN_K(V_, M_) k_bn_post_bwd<V_, M_, false>
+    BN_DISPATCH(V, mode, BN_K, <<<grid, BN_THREADS, 0, st>>>(grad_out, x, N, C, q.G, q.GW, q.RB, gamma, beta, save_mean, save_invstd,
+                                                            nullptr, keep, sd, p, keep_scale, nullptr, part));
+#undef BN_K
+    k_bn_reduce_sums<2><<<C, BN_THREADS, 0, st>>>(part, q.nbx, C, N, gamma, grad_beta, grad_gamma, m12);
+#define BN_K(V_, M_) k_bn_post_bwd<V_, M_, true>
+    BN_DISPATCH(V, mode, BN_K, <<<grid, BN_THREADS, 0, st>>>(grad_out, x, N, C, q.G, q.GW, q.RB, gamma, beta, save_mean, save_invstd,
+                                                            m12, keep, sd, p, keep_scale, grad_x, nullptr));
+#undef BN_K
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }

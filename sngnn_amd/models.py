@@ -23,6 +23,26 @@ FUSE_HIDDEN = os.environ.get("SNGNN_FUSE_HIDDEN", "1") != "0"
 FUSE_BN = os.environ.get("SNGNN_FUSE_BN", "1") != "0"
 
 
+def dropout_seeds(module, device, count):
+    """``count`` int64 counters on ``device`` kept with ``module`` for the in-kernel dropout draws: started
+    from torch's CPU generator (so ``torch.manual_seed`` makes a run reproducible) and advanced on
+    the device once per training forward - inside a captured epoch too, where every replay must
+    drop differently.  The counters are CREATED outside any capture (a host-to-device copy of
+    pageable memory inside one would either fail or be replayed: the same mask every epoch):
+    the model's ``prepare_capture`` does it for a trainer, the first eager training forward otherwise."""
+    s = getattr(module, "_drop_seed", None)
+    if s is None or s.device != device or s.numel() != count:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the dropout seeds must exist before a graph capture: call "
+                               "model.prepare_capture(device) (GraphedEpoch does) or run one eager "
+                               "training forward first")
+        s = torch.randint(0, 2 ** 62, (count,), dtype=torch.int64).to(device)
+        module._drop_seed = s
+    else:
+        s.add_(1)
+    return s
+
+
 class _Stack(nn.Module):
     def reset_parameters(self):
         for lin in self.lins:
@@ -148,23 +168,8 @@ class _Stack(nn.Module):
         return F.log_softmax(self.forward_logits(data), dim=1)
 
     def _dropout_seeds(self, device):
-        """One counter per hidden layer for the in-kernel dropout draw (ops.HiddenEpilogue): started
-        from torch's CPU generator (so ``torch.manual_seed`` makes a run reproducible) and advanced on
-        the device once per training forward - inside a captured epoch too, where every replay must
-        drop differently.  The counters are CREATED outside any capture (a host-to-device copy of
-        pageable memory inside one would either fail or be replayed: the same mask every epoch):
-        :meth:`prepare_capture` does it for a trainer, the first eager training forward otherwise."""
-        s = getattr(self, "_drop_seed", None)
-        if s is None or s.device != device or s.numel() != len(self.lins) - 1:
-            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("the dropout seeds must exist before a graph capture: call "
-                                   "model.prepare_capture(device) (GraphedEpoch does) or run one eager "
-                                   "training forward first")
-            s = torch.randint(0, 2 ** 62, (len(self.lins) - 1,), dtype=torch.int64).to(device)
-            self._drop_seed = s
-        else:
-            s.add_(1)
-        return s
+        """One counter per hidden layer for the in-kernel dropout draw (ops.HiddenEpilogue): :func:`dropout_seeds`."""
+        return dropout_seeds(self, device, len(self.lins) - 1)
 
     def prepare_capture(self, device) -> None:
         """Everything a training forward creates lazily on the host, created now - call before
