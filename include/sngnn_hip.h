@@ -810,6 +810,55 @@ int sngnn_gcn2_map(const float *s, const float *w, float c0, float c1, int64_t N
                    const float *rm, const float *invstd, const float *gamma, const float *beta_bn, float *out,
                    void *stream);
 
+/* ------------------------------------------------------------------------
+ * GCNConv, GCN / GCNJK and MixHop (models/models.py:539-580, 693-843): csrc/gcn.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * One hop over A^ = D^-1/2 (A + I) D^-1/2 (the graph of sngnn_prop_* / sngnn_gcn2_*; any other: SNGNN_EINVAL) on a
+ * COLUMN SLICE of a wider table, with a split store:
+ *     z_i = dinv_i * sum_{e -> i} dinv_src * src[src_row, 0 .. W)
+ * sngnn_gcn2_hop's skeleton (lane group up to 16 in-edges, wave up to 128, 128-edge tasks + a finalize; rows gathered
+ * unscaled, dinv[src] loaded next to the column id; fixed summation order, no floating-point atomics, no host
+ * synchronisation; every product and sum rounded separately).  The first W0 columns of z go to dst0, the other
+ * W - W0 to dst1 (NULL iff W0 == W).  Wp > 0: Wp columns of row i of pass_src are copied to pass_dst by whoever
+ * completes row i (MixHop's un-propagated slice).  Epilogue on the dst0 columns only, each step rounded:
+ *     bias [W0]:                        z = z + bias
+ *     rm, invstd, gamma, beta_bn [W0]:  z = ((z - rm) * invstd) * gamma + beta_bn      (all four or none)
+ *     relu != 0:                        z = max(z, 0)
+ * transpose != 0 walks the out-edges (A^T, the backward's hop).
+ *
+ * Every table pointer addresses column 0 of its slice; ld_* is its row stride in floats (>= the slice's width).
+ * Limits: 1 <= W0 <= W <= SNGNN_MAX_CHANNELS, 0 <= Wp <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE otherwise).  The lane
+ * layout is that of W channels (so the summation order depends on W and the graph alone), the vector width vec is
+ * the largest of 4, 2, 1 that divides W, W0, Wp, every stride and every table pointer's offset (in floats) from a
+ * 16-byte boundary - a lane's vec channels never straddle the W0 boundary.  A narrower vec than W's own multiplies
+ * the steps per lane; more than 8: SNGNN_ERANGE.  A destination (dst0, dst1, pass_dst) must not share an element with
+ * the source, pass_src or another destination (SNGNN_EINVAL; nothing is launched): their address ranges
+ * [p, p + (N - 1) ld + width) are disjoint, or they are disjoint column ranges of one table (equal strides) - a
+ * MixHop launch writes one slice of the output and copies into another.
+ *   workspace   sngnn_gcn_workspace_bytes(g, W): the split rows' task partials of either side (and the partial
+ *               column sums of sngnn_gcn_bias_grad at C = W)
+ *
+ * sngnn_gcn_bias_grad: grad_bias[c] = sum_i g[i, c] (GCNConv's bias), accumulated in double in a fixed order
+ * (per-workgroup partials, then one pass over them), rounded to fp32 once.  g dev f32 [N, C], dense.
+ * Both only enqueue.
+ */
+typedef struct sngnn_gcn_hop {
+    const float *src;       int64_t ld_src;
+    int W, W0;
+    float *dst0;            int64_t ld0;
+    float *dst1;            int64_t ld1;
+    const float *pass_src;  int64_t ld_ps;
+    float *pass_dst;        int64_t ld_pd;
+    int Wp;
+    int relu;
+    const float *bias, *rm, *invstd, *gamma, *beta_bn;
+} sngnn_gcn_hop_t;
+int64_t sngnn_gcn_workspace_bytes(const sngnn_graph_t *g, int W);
+int sngnn_gcn_hop(const sngnn_graph_t *g, const sngnn_gcn_hop_t *a, const float *dinv, int transpose,
+                  void *workspace, void *stream);
+int sngnn_gcn_bias_grad(const float *g, int64_t N, int C, float *grad_bias, void *workspace, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -7,6 +7,7 @@ from .acmgcn import ACMGCN, GraphConvolution2
 from .conv import AGNNConv, SNConv, SNConv_plus, SNConv_plus_plus
 from .gatnet import GAT, GATConv
 from .gcnii import GCN2Conv, GCNII
+from .gcnnet import GCN, GCNJK, GCNConv, MixHop, MixHopLayer
 from .ggcn import GGCN, GGCNlayer_SP
 from .gpr import APPNP, APPNP_Net, GPR_prop, GPRGNN, MLP
 from .models import AGNN, SNGNN, SNGNN_Plus, SNGNN_Plus_Plus
@@ -15,4 +16,4 @@ from .synth import Data
 __all__ = ["SNConv", "SNConv_plus", "SNConv_plus_plus", "SNGNN", "SNGNN_Plus",
            "SNGNN_Plus_Plus", "AGNNConv", "AGNN", "GGCNlayer_SP", "GGCN", "MLP", "GPR_prop",
            "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "GraphConvolution2", "ACMGCN", "GCN2Conv",
-           "GCNII", "Data"]
+           "GCNII", "GCNConv", "GCN", "GCNJK", "MixHopLayer", "MixHop", "Data"]

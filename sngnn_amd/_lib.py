@@ -104,6 +104,9 @@ SIGNATURES = {
     "sngnn_gcn2_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_gcn2_hop": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_gcn2_map": (_i32, [_vp, _vp, _f32, _f32, _i64, _i32, _i32] + [_vp] * 6),
+    "sngnn_gcn_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_gcn_hop": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "sngnn_gcn_bias_grad": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),
@@ -153,8 +156,17 @@ class Epilogue(C.Structure):
                 ("head_workspace", C.c_void_p), ("no_filter", C.c_int)]
 
 
+class GcnHop(C.Structure):
+    """``sngnn_gcn_hop_t`` (include/sngnn_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("ld_src", C.c_int64), ("W", C.c_int), ("W0", C.c_int),
+                ("dst0", C.c_void_p), ("ld0", C.c_int64), ("dst1", C.c_void_p), ("ld1", C.c_int64),
+                ("pass_src", C.c_void_p), ("ld_ps", C.c_int64), ("pass_dst", C.c_void_p), ("ld_pd", C.c_int64),
+                ("Wp", C.c_int), ("relu", C.c_int), ("bias", C.c_void_p), ("rm", C.c_void_p), ("invstd", C.c_void_p),
+                ("gamma", C.c_void_p), ("beta_bn", C.c_void_p)]
+
+
 _lib = None
-_entries = {}          # name -> bound function of every entry ``call`` may enter (filled by load)
+_entries = {}         # name -> bound function of every entry ``call`` may enter (filled by load)
 
 
 class SngnnError(RuntimeError):

@@ -17,6 +17,7 @@ from ._rows import HALF_DTYPES, check_flat as _check_flat, check_grad_dtype as _
 from .acm import acm_filterbank, acm_filterbank_fused, acm_filterbank_plain  # noqa: F401  (csrc/acm.hip)
 from .batchnorm import _BatchNormAct, batch_norm_act, batch_norm_post_act, bn_train_workspace  # noqa: F401  (csrc/batchnorm.hip)
 from .gat import gat_propagate  # noqa: F401  (csrc/gat.hip)
+from .gcn import gcn_conv, gcn_conv_plain, mixhop_plain, mixhop_propagate  # noqa: F401  (csrc/gcn.hip)
 from .gcn2 import gcn2_conv, gcn2_conv_plain, gcn2_map  # noqa: F401  (csrc/gcn2.hip)
 from .graph import Graph
 from .prop import _WeightedPropagate, appnp_propagate, gpr_propagate, weighted_propagate  # noqa: F401  (csrc/prop.hip)
