@@ -859,6 +859,61 @@ int sngnn_gcn_hop(const sngnn_graph_t *g, const sngnn_gcn_hop_t *a, const float 
                   void *workspace, void *stream);
 int sngnn_gcn_bias_grad(const float *g, int64_t N, int C, float *grad_bias, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------
+ * H2GCN (models/models.py:903-1024): csrc/h2gcn.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * The strict two-hop adjacency, replacing H2GCN.init_adj's torch_sparse / scipy passes on the host.  g is the
+ * loop-free graph A1: unpartitioned, built with add_loops = 0, remove_loops = 1 (entry (i, j) per edge j -> i,
+ * duplicates kept); anything else: SNGNN_EINVAL, nothing launched.  Row i of
+ *     A2 = [(A1 A1 != 0) - diag - A1 > 0]
+ * holds every k with k -> j -> i for some j, k != i, (i, k) not an entry of A1; multiplicities play no part.
+ *   sngnn_two_hop_count   count dev i32 [N]: the exact number of entries of every row of A2
+ *   sngnn_two_hop_fill    offsets dev i64 [N]: the exclusive scan of count (the caller's), E2 its total; edge_index dev
+ *                         i64 [2, E2] in canonical order - row 1 the targets, ascending, row 0 the sources, ascending
+ *                         within a target - which sngnn_graph_create takes.  E2 > 2^31 - 1: SNGNN_ERANGE.
+ * One workgroup per row.  A row whose candidate bound sum_{j in N(i)} deg(j) is at most SNGNN_TWO_HOP_HASH_MAX goes
+ * through an open-addressing table in LDS (sorted for the fill); a larger one through a bitmap of N bits in the
+ * workspace, read in order.  Integer atomics only; exact and deterministic.
+ *   workspace   sngnn_two_hop_workspace_bytes(g): the bitmaps (cleared by each call)
+ * Both only enqueue.
+ *
+ * sngnn_h2gcn_dinv: dinv[i] = deg_i^-1/2 of a loop-free graph's row (in-)degree, 0 for an empty row (gcn_norm with
+ * add_self_loops = False); dev f32 [N].  sngnn_prop_dinv keeps refusing such graphs.
+ *
+ * sngnn_h2gcn_hop: one H2GCNConv on A^s = D_s^-1/2 A_s D_s^-1/2 (s = 1, 2; g1 and g2 loop-free graphs of the same N,
+ * dinv1 / dinv2 from sngnn_h2gcn_dinv; the row degree on BOTH sides of the product):
+ *     transpose == 0   dst[:, 0:W] = A^1 src,  dst[:, W:2W] = A^2 src            src [N, W], dst [N, 2W]
+ *     transpose != 0   dst[:, 0:W] = A^1T src[:, 0:W] + A^2T src[:, W:2W]        src [N, 2W], dst [N, W]
+ * sngnn_gcn_hop's skeleton, arithmetic and slice rules (src / dst address column 0 of a column slice, ld_* its row
+ * stride in floats; the lane layout is that of W channels, the vector width the largest of 4, 2, 1 that divides W, both
+ * strides and both pointers' offsets from a 16-byte boundary; more than 8 steps per lane: SNGNN_ERANGE).  The forward is
+ * one launch over the work lists of both graphs and one finalize where either has split rows; the transpose is that
+ * sequence twice, the second adding into the first's stores (no floating-point atomics; each element's sum is
+ * first + second).  A source whose dinv is 0 is multiplied, not skipped; a row without entries stores exact zeros.
+ * Epilogue (transpose == 0 only; all four or none), on all 2W columns, each step rounded:
+ *     rm, invstd, gamma, beta_bn [2W]:  z = ((z - rm) * invstd) * gamma + beta_bn
+ * Limits: 1 <= W <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE); dst must not share an element with src as in sngnn_gcn_hop,
+ * partitioned graphs, graphs with loops added, mismatched N or NULL: SNGNN_EINVAL.  Refused calls launch nothing.
+ *   workspace1 / workspace2   sngnn_h2gcn_workspace_bytes(g1 / g2, W): the split rows' task partials of either side
+ * Only enqueues.
+ */
+#define SNGNN_TWO_HOP_HASH_MAX 1024
+typedef struct sngnn_h2gcn_hop {
+    const float *src;  int64_t ld_src;
+    float *dst;        int64_t ld_dst;
+    int W;
+    const float *rm, *invstd, *gamma, *beta_bn;
+} sngnn_h2gcn_hop_t;
+int64_t sngnn_two_hop_workspace_bytes(const sngnn_graph_t *g);
+int sngnn_two_hop_count(const sngnn_graph_t *g, int32_t *count, void *workspace, void *stream);
+int sngnn_two_hop_fill(const sngnn_graph_t *g, const int64_t *offsets, int64_t E2, int64_t *edge_index,
+                       void *workspace, void *stream);
+int sngnn_h2gcn_dinv(const sngnn_graph_t *g, float *dinv, void *stream);
+int64_t sngnn_h2gcn_workspace_bytes(const sngnn_graph_t *g, int W);
+int sngnn_h2gcn_hop(const sngnn_graph_t *g1, const sngnn_graph_t *g2, const sngnn_h2gcn_hop_t *a, const float *dinv1,
+                    const float *dinv2, int transpose, void *workspace1, void *workspace2, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

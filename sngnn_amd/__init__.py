@@ -9,6 +9,7 @@ from .gatnet import GAT, GATConv
 from .gcnii import GCN2Conv, GCNII
 from .gcnnet import GCN, GCNJK, GCNConv, MixHop, MixHopLayer
 from .ggcn import GGCN, GGCNlayer_SP
+from .h2gcnnet import H2GCN, H2GCNConv
 from .gpr import APPNP, APPNP_Net, GPR_prop, GPRGNN, MLP
 from .models import AGNN, SNGNN, SNGNN_Plus, SNGNN_Plus_Plus
 from .synth import Data
@@ -16,4 +17,5 @@ from .synth import Data
 __all__ = ["SNConv", "SNConv_plus", "SNConv_plus_plus", "SNGNN", "SNGNN_Plus",
            "SNGNN_Plus_Plus", "AGNNConv", "AGNN", "GGCNlayer_SP", "GGCN", "MLP", "GPR_prop",
            "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "GraphConvolution2", "ACMGCN", "GCN2Conv",
-           "GCNII", "GCNConv", "GCN", "GCNJK", "MixHopLayer", "MixHop", "Data"]
+           "GCNII", "GCNConv", "GCN", "GCNJK", "MixHopLayer", "MixHop", "H2GCNConv",
+           "H2GCN", "Data"]

@@ -21,6 +21,7 @@ DTYPE_F16, DTYPE_BF16 = 1, 2          # SNGNN_DTYPE_*: storage types of the half
 UNSELECTED = -4.0
 LOOPS_REPLACE = 2      # SNGNN_LOOPS_REPLACE: drop the original loops, then append one per node
 MAX_CHANNELS = 512
+TWO_HOP_HASH_MAX = 1024    # SNGNN_TWO_HOP_HASH_MAX: the widest candidate bound the two-hop build keeps in an LDS table
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
@@ -107,6 +108,12 @@ SIGNATURES = {
     "sngnn_gcn_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_gcn_hop": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "sngnn_gcn_bias_grad": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
+    "sngnn_two_hop_workspace_bytes": (_i64, [_vp]),
+    "sngnn_two_hop_count": (_i32, [_vp, _vp, _vp, _vp]),
+    "sngnn_two_hop_fill": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sngnn_h2gcn_dinv": (_i32, [_vp, _vp, _vp]),
+    "sngnn_h2gcn_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_h2gcn_hop": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),
@@ -165,8 +172,14 @@ class GcnHop(C.Structure):
                 ("gamma", C.c_void_p), ("beta_bn", C.c_void_p)]
 
 
+class H2gcnHop(C.Structure):
+    """``sngnn_h2gcn_hop_t`` (include/sngnn_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("ld_src", C.c_int64), ("dst", C.c_void_p), ("ld_dst", C.c_int64), ("W", C.c_int),
+                ("rm", C.c_void_p), ("invstd", C.c_void_p), ("gamma", C.c_void_p), ("beta_bn", C.c_void_p)]
+
+
 _lib = None
-_entries = {}         # name -> bound function of every entry ``call`` may enter (filled by load)
+_entries = {}        # name -> bound function of every entry ``call`` may enter (filled by load)
 
 
 class SngnnError(RuntimeError):

@@ -467,6 +467,14 @@ template <int VEC, int G, int R> struct Row {
     }
 };
 
+// VEC consecutive floats in one store
+template <int VEC> __device__ __forceinline__ void store_vec(float *p, const float (&x)[VEC])
+{
+    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]);
+    else if constexpr (VEC == 2) *reinterpret_cast<float2 *>(p) = make_float2(x[0], x[1]);
+    else p[0] = x[0];
+}
+
 // 1 / max(||row||_2, eps) from the group-summed sum of squares: hardware
 // reciprocal square root of max(sumsq, eps^2) plus one Newton step (about half an
 // ulp; the same bits wherever a row's norm is needed, forward and backward).

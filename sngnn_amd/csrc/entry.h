@@ -87,6 +87,25 @@ inline int check_rows(int C, int dtype, std::initializer_list<const void *> rows
     return SNGNN_OK;
 }
 
+// a column slice: W columns at p of N rows ld floats apart; p == nullptr or W == 0: none
+struct Slice { const float *p; int64_t N, ld, w; };
+
+// whether two slices share an element.  Disjoint address intervals do not; neither do two column ranges of one
+// row-strided table (equal strides, the second's first column d = (pb - pa) mod ld behind the first's last and its
+// last in front of the stride's end) - MixHop's launches write slices of the table they also copy into.  Anything
+// else whose intervals meet counts as sharing.
+inline bool overlap(const Slice &a, const Slice &b)
+{
+    if (!a.p || !b.p || a.w <= 0 || b.w <= 0 || a.N <= 0) return false;
+    const uintptr_t alo = (uintptr_t)a.p, ahi = alo + (uintptr_t)(((a.N - 1) * a.ld + a.w) * 4);
+    const uintptr_t blo = (uintptr_t)b.p, bhi = blo + (uintptr_t)(((b.N - 1) * b.ld + b.w) * 4);
+    if (ahi <= blo || bhi <= alo) return false;
+    if (a.ld != b.ld) return true;
+    const int64_t diff = ((int64_t)blo - (int64_t)alo) / 4;
+    const int64_t d = ((diff % a.ld) + a.ld) % a.ld;
+    return !(d >= a.w && d + b.w <= a.ld);
+}
+
 // ---- dispatch ---------------------------------------------------------------------------------------------------------
 template <typename S> struct Storage { using type = S; };
 

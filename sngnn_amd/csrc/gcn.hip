@@ -79,13 +79,6 @@ __device__ __forceinline__ float gcn_epilogue(const GcnArgs &a, int c, float z)
     return z;
 }
 
-template <int VEC> __device__ __forceinline__ void store_vec(float *p, const float (&x)[VEC])
-{
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]);
-    else if constexpr (VEC == 2) *reinterpret_cast<float2 *>(p) = make_float2(x[0], x[1]);
-    else p[0] = x[0];
-}
-
 // row r from its gathered sum s: the scale by dinv_r, the split store, the pass-through copy (G lanes)
 template <int VEC, int G, int R>
 __device__ __forceinline__ void gcn_finish(const GcnArgs &a, int r, int lg, Row<VEC, G, R> &s)
@@ -245,25 +238,6 @@ static int gcn_hop_vec(const sngnn_gcn_hop_t *h)
         bits |= ((uintptr_t)h->pass_src >> 2) | ((uintptr_t)h->pass_dst >> 2);
     }
     return bits % 4 == 0 ? 4 : bits % 2 == 0 ? 2 : 1;
-}
-
-// a column slice: W columns at p of N rows ld floats apart; p == nullptr or W == 0: none
-struct Slice { const float *p; int64_t N, ld, w; };
-
-// whether two slices share an element.  Disjoint address intervals do not; neither do two column ranges of one
-// row-strided table (equal strides, the second's first column d = (pb - pa) mod ld behind the first's last and its
-// last in front of the stride's end) - MixHop's launches write slices of the table they also copy into.  Anything
-// else whose intervals meet counts as sharing.
-static bool overlap(const Slice &a, const Slice &b)
-{
-    if (!a.p || !b.p || a.w <= 0 || b.w <= 0 || a.N <= 0) return false;
-    const uintptr_t alo = (uintptr_t)a.p, ahi = alo + (uintptr_t)(((a.N - 1) * a.ld + a.w) * 4);
-    const uintptr_t blo = (uintptr_t)b.p, bhi = blo + (uintptr_t)(((b.N - 1) * b.ld + b.w) * 4);
-    if (ahi <= blo || bhi <= alo) return false;
-    if (a.ld != b.ld) return true;
-    const int64_t diff = ((int64_t)blo - (int64_t)alo) / 4;
-    const int64_t d = ((diff % a.ld) + a.ld) % a.ld;
-    return !(d >= a.w && d + b.w <= a.ld);
 }
 
 // per-workgroup partial column sums in double: workgroup b takes the rows b * 4 + q, + 4 gridDim.x, ... (q = the
