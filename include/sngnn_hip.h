@@ -726,6 +726,60 @@ int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out, const floa
                        void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Weighted relational graph attention (WRGAT): csrc/wrgat.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * WeightedRGATConv (models.py:1903-2014) after its linear maps, for P [N, R, C] with P[n,r,:] = x[n] weight[r] (R
+ * relations of C channels), atten [R, 2C] = [target half | source half], edges e = (j -> i) of relation r_e and weight
+ * w_e:
+ *     s_dst[n,r] = <P[n,r], atten[r,:C]>,  s_src[n,r] = <P[n,r], atten[r,C:]>,  a_e = leaky_relu(s_dst[i,r] + s_src[j,r])
+ *     per segment (i, r) of n_ir edges:  alpha_e = exp(a_e - m_ir) / (l_ir + 1e-16),  m_ir = max a_e, l_ir = sum exp(a_e - m_ir)
+ *     out[i] = sum_r (1 / n_ir) sum_{e in (i,r)} w_e alpha_e P[j,r,:]  +  self_rows[i]  +  bias      (relu: max(., 0))
+ * - a softmax per relation AND target, averaged over the relation's edges, all relations added into one row (the
+ * reference: R masked propagate calls with [E_r, C] messages).  A non-empty segment holds its maximum, so l_ir >= 1 and
+ * the 1e-16 vanishes in fp32; an empty segment adds exactly 0.
+ *
+ * The graph: the edge list sorted STABLY by relation, built with add_loops = 0, remove_loops = 0 (every edge kept,
+ * duplicates count once each), unpartitioned (SNGNN_EINVAL otherwise).  Its CSR rows are then grouped by relation:
+ *   rel_ptr  dev i32 [N, R + 1]   offsets inside the row: entries [rel_ptr[i,r], rel_ptr[i,r+1]) of row i carry relation r
+ *   rel_csc  dev i32 [E]          the relation of every CSC entry (the backward's scatter pass)
+ *   w_csr    dev f32 [E]          the edge weights in CSR order, or NULL (= 1); data, no gradient
+ * Limits: 1 <= R <= 16, C >= 1, R * C <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE otherwise, nothing launched).
+ * P, self_rows, grad_P and grad_self are row-strided (strides in floats, multiples of the row vector width 4 | 2 | 1
+ * that divides C): slices of one [N, R * C + C] table.  Row classes of the other gather kernels; fixed summation
+ * order, no floating-point atomics, no host synchronisation.
+ */
+/* bytes of device workspace of the two entries below; 0 outside the limits */
+int64_t sngnn_wrgat_workspace_bytes(const sngnn_graph_t *g, int R, int C);
+/*
+ * Replaces: models.py:1975-1993 and :1997-2008 - per relation a masked edge list, a matmul, the gathers of x_i / x_j,
+ * cat, leaky_relu, PyG's softmax, two [E_r, C] products, the scatter-mean and an add.  Launches: the score pass of
+ * sngnn_gat_scores (H = R), the statistics m, l [N, R] from a 4-byte gather per edge (+ a finalize on [tasks, R]
+ * scalars for split rows), and one weighted gather-sum that fetches only the slice P[j, r_e, :] per edge (+ a plain
+ * finalize), root slice, bias and relu in its store.
+ *   self_rows, bias  may be NULL       out  dev f32 [N, C] dense
+ *   scores  dev f32 [2, N, R] (out)    s_src then s_dst       ml  dev f32 [2, N, R] (out)   m then l
+ */
+int sngnn_wrgat_forward(const sngnn_graph_t *g, const float *P, int64_t P_stride, const float *self_rows,
+                        int64_t self_stride, const float *bias, const int32_t *rel_ptr, const float *w_csr,
+                        const float *atten, int R, int C, float negative_slope, int relu, float *out, float *scores,
+                        float *ml, void *workspace, void *stream);
+/*
+ * Replaces: autograd through the sequence above.  With G = grad_out, zeroed where relu gave out <= 0 (out is read
+ * only then), t_e = <G_i, P[j,r]>, D_ir = sum_{(i,r)} alpha_e w_e t_e, ds_e = alpha_e (w_e t_e - D_ir) / n_ir,
+ * da_e = ds_e leaky'(raw_e):
+ *   grad_P[j,r,:] = sum_{e out of j, type r} (w_e alpha_e / n_ir) G_i + grad_s_src[j,r] atten[r,C:] + grad_s_dst[j,r] atten[r,:C]
+ *   grad_atten [R, 2C] = [sum_n grad_s_dst[n,r] P[n,r,:] | sum_n grad_s_src[n,r] P[n,r,:]]  (f64 partials, fixed order)
+ *   grad_self = G (masked), grad_bias = its column sums (f64 partials, fixed order)
+ * Each of grad_P, grad_self, grad_atten, grad_bias may be NULL (not wanted).
+ */
+int sngnn_wrgat_backward(const sngnn_graph_t *g, const float *grad_out, const float *out, const float *P,
+                         int64_t P_stride, const int32_t *rel_ptr, const int32_t *rel_csc, const float *w_csr,
+                         const float *atten, const float *scores, const float *ml, int R, int C,
+                         float negative_slope, int relu, float *grad_P, int64_t grad_P_stride, float *grad_self,
+                         int64_t grad_self_stride, float *grad_atten, float *grad_bias, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------
  * ACM-GCN's low / high / identity filterbank with its three-way attention: csrc/acm.hip.
  * ------------------------------------------------------------------------ */
 /*

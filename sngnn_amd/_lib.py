@@ -99,6 +99,9 @@ SIGNATURES = {
     "sngnn_gat_workspace_bytes": (_i64, [_vp, _i32, _i32]), "sngnn_gat_scores": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_gat_forward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "sngnn_gat_backward": (_i32, [_vp] * 9 + [_i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "sngnn_wrgat_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "sngnn_wrgat_forward": (_i32, [_vp, _vp, _i64, _vp, _i64] + [_vp] * 4 + [_i32, _i32, _f32, _i32] + [_vp] * 5),
+    "sngnn_wrgat_backward": (_i32, [_vp] * 4 + [_i64] + [_vp] * 6 + [_i32, _i32, _f32, _i32, _vp, _i64, _vp, _i64] + [_vp] * 4),
     "sngnn_acm_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_acm_forward": (_i32, [_vp] * 6 + [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_acm_backward": (_i32, [_vp] * 9 + [_i32, _i32, _vp, _vp, _vp, _vp]),

@@ -350,15 +350,17 @@ static __global__ __launch_bounds__(256) void k_gat_bwd_s_fin(const GatArgs a)
 }
 
 // the score pass: a_src and a_dst [N, H] from one read of xp; the C products of a score are summed in double and
-// rounded once
-static __global__ __launch_bounds__(256) void k_gat_scores(const float *__restrict__ xp, const float *__restrict__ att_src,
-                                                           const float *__restrict__ att_dst, int64_t NH, int H, int C,
-                                                           float *__restrict__ asrc, float *__restrict__ adst)
+// rounded once.  Rows of xp are ld floats apart, rows of att_* lda (dense: H * C and C).
+static __global__ __launch_bounds__(256) void k_gat_scores(const float *__restrict__ xp, int64_t ld,
+                                                           const float *__restrict__ att_src,
+                                                           const float *__restrict__ att_dst, int64_t lda, int64_t NH,
+                                                           int H, int C, float *__restrict__ asrc,
+                                                           float *__restrict__ adst)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= NH) return;
     const int h = (int)(i % H);
-    const float *row = xp + i * C, *ws = att_src + h * C, *wd = att_dst + h * C;
+    const float *row = xp + (i / H) * ld + (int64_t)h * C, *ws = att_src + h * lda, *wd = att_dst + h * lda;
     double s = 0.0, d = 0.0;
     for (int c = 0; c < C; ++c) {
         const double v = (double)row[c];
@@ -370,7 +372,8 @@ static __global__ __launch_bounds__(256) void k_gat_scores(const float *__restri
 }
 
 // grad_att: workgroup b's partial sums over its npb nodes, in double: part [B, 2, W]
-static __global__ __launch_bounds__(256) void k_gat_att_part(const float *__restrict__ xp, const float *__restrict__ gasrc,
+static __global__ __launch_bounds__(256) void k_gat_att_part(const float *__restrict__ xp, int64_t ld,
+                                                             const float *__restrict__ gasrc,
                                                              const float *__restrict__ gadst, int N, int H, int C, int npb,
                                                              double *__restrict__ part)
 {
@@ -380,7 +383,7 @@ static __global__ __launch_bounds__(256) void k_gat_att_part(const float *__rest
         const int h = c / C;
         double s = 0.0, d = 0.0;
         for (int n = n0; n < n1; ++n) {
-            const double v = (double)xp[(size_t)n * W + c];
+            const double v = (double)xp[(size_t)n * ld + c];
             s += (double)gasrc[(size_t)n * H + h] * v;
             d += (double)gadst[(size_t)n * H + h] * v;
         }
@@ -454,6 +457,25 @@ GAT_DISPATCH(dispatch_gat_bwd_s, launch_gat_bwd_s)
 
 static int gat_att_npb(int64_t N) { return (int)std::max<int64_t>(8, (N + GAT_ATT_BLOCKS - 1) / GAT_ATT_BLOCKS); }
 
+// (common.h: the score pass and the grad_att partials on rows ld floats apart - wrgat.hip enters them too)
+int gat_att_blocks(int64_t N) { return ceil_div(std::max<int64_t>(N, 1), gat_att_npb(N)); }
+
+int launch_gat_scores(const float *xp, int64_t ld, const float *att_src, const float *att_dst, int64_t lda, int64_t N,
+                      int H, int C, float *a_src, float *a_dst, hipStream_t st)
+{
+    k_gat_scores<<<ceil_div(N * H, 256), 256, 0, st>>>(xp, ld, att_src, att_dst, lda, N * H, H, C, a_src, a_dst);
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+int launch_gat_att_part(const float *xp, int64_t ld, const float *gasrc, const float *gadst, int64_t N, int H, int C,
+                        double *part, hipStream_t st)
+{
+    k_gat_att_part<<<gat_att_blocks(N), 256, 0, st>>>(xp, ld, gasrc, gadst, (int)N, H, C, gat_att_npb(N), part);
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
 // workspace regions (256-byte aligned): the tasks' partial rows | their two scalars per head | the edge records |
 // grad_a_src | grad_a_dst | the grad_att partials
 struct GatLayout { int64_t tml, rec, gasrc, gadst, att, total; };
@@ -467,7 +489,7 @@ static GatLayout gat_layout(const sngnn_graph_t *g, int H, int C)
     L.gasrc = L.rec + up256(g->Ep * H * 2 * 4);
     L.gadst = L.gasrc + up256(g->N * H * 4);
     L.att = L.gadst + up256(g->N * H * 4);
-    L.total = L.att + up256((int64_t)ceil_div(std::max<int64_t>(g->N, 1), gat_att_npb(g->N)) * 2 * H * C * 8);
+    L.total = L.att + up256((int64_t)gat_att_blocks(g->N) * 2 * H * C * 8);
     return L;
 }
 
@@ -503,9 +525,7 @@ extern "C" int sngnn_gat_scores(const float *xp, const float *att_src, const flo
     SN_REQUIRE(N >= 0 && N * (int64_t)H < (int64_t)1 << 31, SNGNN_ERANGE, "N * heads must fit 31 bits");
     if (N == 0) return SNGNN_OK;
     SN_REQUIRE(xp && att_src && att_dst && a_src && a_dst, SNGNN_EINVAL, "NULL argument");
-    k_gat_scores<<<ceil_div(N * H, 256), 256, 0, (hipStream_t)stream>>>(xp, att_src, att_dst, N * H, H, C, a_src, a_dst);
-    SN_HIP(hipGetLastError());
-    return SNGNN_OK;
+    return launch_gat_scores(xp, (int64_t)H * C, att_src, att_dst, C, N, H, C, a_src, a_dst, (hipStream_t)stream);
 }
 
 extern "C" int sngnn_gat_forward(const sngnn_graph_t *g, const float *xp, const float *a_src, const float *a_dst, int H,
@@ -559,10 +579,10 @@ extern "C" int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out,
     rc = dispatch_gat_bwd_s(cfg, a, st);
     if (rc != SNGNN_OK) return rc;
     if (grad_att) {
-        const int npb = gat_att_npb(g->N), B = ceil_div(g->N, npb);
         double *part = (double *)((char *)workspace + L.att);
-        k_gat_att_part<<<B, 256, 0, st>>>(xp, a.gasrc, a.gadst, (int)g->N, H, C, npb, part);
-        k_gat_att_red<<<ceil_div(2 * H * C, 256), 256, 0, st>>>(part, B, H * C, grad_att);
+        rc = launch_gat_att_part(xp, (int64_t)H * C, a.gasrc, a.gadst, g->N, H, C, part, st);
+        if (rc != SNGNN_OK) return rc;
+        k_gat_att_red<<<ceil_div(2 * H * C, 256), 256, 0, st>>>(part, gat_att_blocks(g->N), H * C, grad_att);
         SN_HIP(hipGetLastError());
     }
     return SNGNN_OK;

@@ -157,6 +157,12 @@ class GraphCache:
             self._recording.append(hit[0])
         return hit[0]
 
+    def note(self, graph: Graph) -> None:
+        """A graph built outside this cache (the relation-sorted graph of ``ops.TypedAdjacency``) that a forward is
+        about to launch on: collected by an active :meth:`record` like the graphs ``get`` hands out."""
+        if self._recording is not None and not any(g is graph for g in self._recording):
+            self._recording.append(graph)
+
     def record(self):
         """Context manager: collects the Graph objects ``get`` hands out inside it (the graphs a
         captured epoch launches on - what its owner must keep alive)."""
