@@ -968,6 +968,62 @@ int64_t sngnn_h2gcn_workspace_bytes(const sngnn_graph_t *g, int W);
 int sngnn_h2gcn_hop(const sngnn_graph_t *g1, const sngnn_graph_t *g2, const sngnn_h2gcn_hop_t *a, const float *dinv1,
                     const float *dinv2, int transpose, void *workspace1, void *workspace2, void *stream);
 
+/* ------------------------------------------------------------------------
+ * MLPNORM's norm layer (GloGNN, models/models.py:1389-1437) on the sparse graph: csrc/glognn.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * Replaces: norm_func1 / norm_func2 with order_func1 / order_func2 on to_dense_adj's [N, N] matrix (about 25 torch
+ * ops, norm_layers x orders dense N x N products, one torch.inverse) for fp32 rows of 1 <= C <= SNGNN_GLOGNN_MAX_C
+ * channels (SNGNN_ERANGE otherwise).  With coe = 1/(alpha+beta), coe1 = 1-gamma, coe2 = 1/coe1, s = coe/coe1,
+ * D = diag(diag) (I when diag is NULL), G = x^T x, V = (coe2^2 I + coe G)^-1:
+ *     M = s V D,   T = s D G V D,   W = G V,   S = sum_k w_k A^k x,
+ *     out = coe1 (x - gamma h0) T + beta S M + gamma h0
+ * A is to_dense_adj's matrix, (A v)_i = sum over the edges with edge_index[0] == i of v[edge_index[1]] (duplicates
+ * counted, loops kept): the CSC side of the unpartitioned graph built with add_loops = 0, remove_loops = 0
+ * (SNGNN_EINVAL otherwise) - sngnn_adj_linear_forward's orientation.  orders_weight NULL is order_func1 (k = 0 .. orders,
+ * w_k = 1), otherwise order_func2 (k = 1 .. orders, w_k = orders_weight[k - 1], dev f32 [orders]).  alpha, beta, gamma
+ * act in double; alpha + beta == 0 or gamma == 1: SNGNN_EINVAL.  No floating-point atomics: the same bits on every
+ * run.  Every entry only enqueues.
+ *
+ * sngnn_glognn_gram: out = (a - sub_scale a_sub)^T b and out2 = a2^T b, dev f64 [C, C], from one read of b; a_sub NULL:
+ *   a^T b; a2 and out2 NULL together: one product.  a, a_sub, a2, b dev f32 [N, C].  32-row tiles through LDS,
+ *   products and sums in double, per-workgroup partials added in workgroup order.
+ *   workspace: sngnn_glognn_gram_workspace_bytes(C) (the first bytes of sngnn_glognn_workspace_bytes's buffer serve).
+ * sngnn_glognn_solve: M, T, V, W dev f64 [C, C] and MT32 dev f32 [2, C, C] (M, then T, rounded) from G: one
+ *   workgroup, Gauss-Jordan in double without pivoting (the matrix is SPD, smallest eigenvalue >= coe2^2).
+ * sngnn_glognn_solve_backward: from gM = scale_m gM, gT = scale_t gT (dev f64 [C, C], the gradients of M and T):
+ *   gV = s gM D + s G D gT D,  gG = s D gT D V - coe V gV V,  gG2 = gG + gG^T,
+ *   grad_diag = s colsum(V o gM) + s rowsum((W D) o gT) + s colsum((D W) o gT)   (dev f64 [C]; NULL: not wanted).
+ *   tmp dev f64 [2, C, C].
+ * sngnn_glognn_forward: the hops t_k = A t_{k-1} (unweighted row gather-sums on the row classes of the other gather
+ *   kernels: lane group, wave, 128-entry tasks + a finalize), S += w_k t_k in their stores, the mix in the last hop's
+ *   store (M, T in LDS, each C x C product per row accumulated in double).  x, h0, S, out dev f32 [N, C], rows aligned
+ *   to 4 * vec bytes; S is kept for the backward.
+ * sngnn_glognn_backward: q = beta g M^T, grad_h0 = gamma g - gamma coe1 g T^T and grad_x = coe1 g T^T [+ q] in a row-
+ *   local pass; r_0 = q, r_k = A^T r_{k-1} on the CSR side with grad_x += w_k r_k in the stores and x gG2 folded into
+ *   the last one; grad_w dev f64 [orders] = <r_k, x> (NULL: not wanted) from per-workgroup partial dots in double,
+ *   added by a reducer in a fixed order.  gG2 is sngnn_glognn_solve_backward's, from gM = beta S^T g and
+ *   gT = coe1 (x - gamma h0)^T g (sngnn_glognn_gram).
+ *   workspace: sngnn_glognn_workspace_bytes(g, C, orders) - the gram partials, two iterates [N, C], the split rows'
+ *   task partials of either side and the dot partials.
+ */
+#define SNGNN_GLOGNN_MAX_C 64
+int64_t sngnn_glognn_gram_workspace_bytes(int C);
+int sngnn_glognn_gram(const float *a, const float *a_sub, double sub_scale, const float *a2, const float *b, int64_t N,
+                      int C, double *out, double *out2, void *workspace, void *stream);
+int sngnn_glognn_solve(const double *G, const float *diag, double alpha, double beta, double gamma, int C, double *M,
+                       double *T, double *V, double *W, float *MT32, void *stream);
+int sngnn_glognn_solve_backward(const double *gM, const double *gT, double scale_m, double scale_t, const double *G,
+                                const double *V, const double *W, const float *diag, double alpha, double beta,
+                                double gamma, int C, double *gG2, double *grad_diag, double *tmp, void *stream);
+int64_t sngnn_glognn_workspace_bytes(const sngnn_graph_t *g, int C, int orders);
+int sngnn_glognn_forward(const sngnn_graph_t *g, const float *x, const float *h0, const float *MT32,
+                         const float *orders_weight, int orders, double beta, double gamma, int C, float *S, float *out,
+                         void *workspace, void *stream);
+int sngnn_glognn_backward(const sngnn_graph_t *g, const float *grad_out, const float *x, const float *MT32,
+                          const double *gG2, const float *orders_weight, int orders, double beta, double gamma, int C,
+                          float *grad_x, float *grad_h0, double *grad_w, void *workspace, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -23,7 +23,7 @@ LOOPS_REPLACE = 2      # SNGNN_LOOPS_REPLACE: drop the original loops, then appe
 MAX_CHANNELS = 512
 TWO_HOP_HASH_MAX = 1024    # SNGNN_TWO_HOP_HASH_MAX: the widest candidate bound the two-hop build keeps in an LDS table
 
-_vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
+_vp, _i64, _i32, _f32, _f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
 
 # name -> (restype, argtypes); mirrors include/sngnn_hip.h one to one
 SIGNATURES = {
@@ -71,8 +71,7 @@ SIGNATURES = {
     "sngnn_attn_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_signed_forward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_signed_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sngnn_blend_workspace_bytes": (_i64, []),
-    "sngnn_blend_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "sngnn_blend_workspace_bytes": (_i64, []), "sngnn_blend_forward": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_blend_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_blend_forward_epilogue": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "sngnn_blend_backward_epilogue": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -91,8 +90,7 @@ SIGNATURES = {
     "sngnn_weighted_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_weighted_scatter_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_pair_dot_rows": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
-    "sngnn_prop_dinv": (_i32, [_vp, _vp, _vp]),
-    "sngnn_prop_workspace_bytes": (_i64, [_vp, _i32, _i32]),
+    "sngnn_prop_dinv": (_i32, [_vp, _vp, _vp]), "sngnn_prop_workspace_bytes": (_i64, [_vp, _i32, _i32]),
     "sngnn_prop_gpr_forward": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_prop_gpr_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_prop_appnp": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -108,15 +106,17 @@ SIGNATURES = {
     "sngnn_gcn2_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_gcn2_hop": (_i32, [_vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_gcn2_map": (_i32, [_vp, _vp, _f32, _f32, _i64, _i32, _i32] + [_vp] * 6),
-    "sngnn_gcn_workspace_bytes": (_i64, [_vp, _i32]),
-    "sngnn_gcn_hop": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
+    "sngnn_gcn_workspace_bytes": (_i64, [_vp, _i32]), "sngnn_gcn_hop": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp]),
     "sngnn_gcn_bias_grad": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
-    "sngnn_two_hop_workspace_bytes": (_i64, [_vp]),
-    "sngnn_two_hop_count": (_i32, [_vp, _vp, _vp, _vp]),
+    "sngnn_two_hop_workspace_bytes": (_i64, [_vp]), "sngnn_two_hop_count": (_i32, [_vp, _vp, _vp, _vp]),
     "sngnn_two_hop_fill": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
-    "sngnn_h2gcn_dinv": (_i32, [_vp, _vp, _vp]),
-    "sngnn_h2gcn_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_h2gcn_dinv": (_i32, [_vp, _vp, _vp]), "sngnn_h2gcn_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_h2gcn_hop": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "sngnn_glognn_gram_workspace_bytes": (_i64, [_i32]), "sngnn_glognn_gram": (_i32, [_vp, _vp, _f64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_glognn_solve": (_i32, [_vp, _vp, _f64, _f64, _f64, _i32] + [_vp] * 6),
+    "sngnn_glognn_solve_backward": (_i32, [_vp, _vp, _f64, _f64] + [_vp] * 4 + [_f64] * 3 + [_i32] + [_vp] * 4),
+    "sngnn_glognn_workspace_bytes": (_i64, [_vp, _i32, _i32]), "sngnn_glognn_forward": (_i32, [_vp] * 5 + [_i32, _f64, _f64, _i32] + [_vp] * 4),
+    "sngnn_glognn_backward": (_i32, [_vp] * 6 + [_i32, _f64, _f64, _i32] + [_vp] * 5),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []),

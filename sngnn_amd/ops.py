@@ -19,6 +19,7 @@ from .batchnorm import _BatchNormAct, batch_norm_act, batch_norm_post_act, bn_tr
 from .gat import gat_propagate  # noqa: F401  (csrc/gat.hip)
 from .gcn import gcn_conv, gcn_conv_plain, mixhop_plain, mixhop_propagate  # noqa: F401  (csrc/gcn.hip)
 from .gcn2 import gcn2_conv, gcn2_conv_plain, gcn2_map  # noqa: F401  (csrc/gcn2.hip)
+from .glognn import adj_matmul, glognn_norm, glognn_norm_plain, glognn_solve, glognn_solve_backward, gram  # noqa: F401  (csrc/glognn.hip)
 from .graph import Graph
 from .h2gcn import H2Adjacency, h2gcn_conv, h2gcn_conv_plain, two_hop_edge_index  # noqa: F401  (csrc/h2gcn.hip)
 from .prop import _WeightedPropagate, appnp_propagate, gpr_propagate, weighted_propagate  # noqa: F401  (csrc/prop.hip)
