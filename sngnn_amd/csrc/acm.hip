@@ -8,7 +8,7 @@
 // adj_high = I - adj_low:  L_i = S^l_i / n_i,  H_i = (1 - 1 / n_i) Ph_i - S^h_i / n_i  with  S^l_i the sum of Pl[col] over
 // row i and S^h_i the sum of Ph[col] over its OFF-diagonal entries (the reference's own terms: with the diagonal
 // inside the sum, Ph_i - Ph_i / n_i cancels - completely for an isolated node - what the reference never adds) -
-// an unweighted gather-sum of one contiguous 2C-wide slice per entry on the skeleton of prop.hip (small rows by lane
+// an unweighted gather-sum of one contiguous 2C-wide slice per entry on the row-class walk of row_walk.h (small rows by lane
 // group, medium rows by wave, hubs as 128-entry tasks + a finalize; fixed summation order, no atomics), n_i from the
 // graph's own rowptr.  Whoever completes a row runs the whole epilogue and stores out, the pre-activations [L | H]
 // and six scalars (d, att) a row: all the backward needs next to P.
@@ -20,14 +20,14 @@
 //                     grad_Ph_j = (1 - 1 / n_j) gH_j - sum_{i != j : j in row i} gH_i / n_i
 // A lane holds the SAME channels of the l and the h half (two rows of the C-wide layout), so the epilogue is
 // lane-local up to three group sums.  Every product and sum is rounded separately (-ffp-contract=off).
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
 constexpr int ACM_PARAM_BLOCKS = 512;       // most workgroups (= partials per parameter gradient) of pass A
 
-struct AcmArgs {
+struct AcmArgs : RowSide {
     const float *src;           // rows gathered: [N, ld], the [l | h] slice in front
     int ld;
     int mode;                   // 0 forward, 1 backward pass B
@@ -38,10 +38,13 @@ struct AcmArgs {
     float *gP;                  // pass B: grad_P [N, 3C]; its h third holds (1 - 1 / n_j) gH_j on entry
     float *partial;             // [n_tasks, 2C]
     int C, N;
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
+};
+
+// a row's two gathered sums: the l half and the h half without the diagonal
+template <int VEC, int G, int R> struct AcmSums {
+    Row<VEC, G, R> l, h;
+    __device__ __forceinline__ void zero() { l.zero(); h.zero(); }
+    __device__ __forceinline__ void reduce_across_groups() { l.reduce_across_groups(); h.reduce_across_groups(); }
 };
 
 // relu that keeps a NaN (torch's)
@@ -158,56 +161,19 @@ __device__ __forceinline__ void acm_finish(const AcmArgs &a, int r, int deg, int
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_acm(const AcmArgs a)
 {
-    using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
-    const int b = blockIdx.x;
-    RowT sl, sh;
-    sl.zero();
-    sh.zero();
-    if (b < a.nbA + a.nbB) {
-        // split task or one wave per row
-        const bool task = b < a.nbA;
-        const int tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        const bool live = task ? tq < a.n_tasks : slot < a.n_med_end;          // (wave-uniform)
-        if (live) {
-            const int seg = a.perm[task ? a.task_slot[tq] : slot];
-            const int e0 = task ? a.task_chunk[tq] * CHUNK : 0;
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            acm_gather<VEC, G, R>(a, seg, qs, e0, e1, NG, gid, lg, sl, sh);
-            sl.reduce_across_groups();
-            sh.reduce_across_groups();
-            if (gid == 0) {
-                if (task) {
-                    float *pt = a.partial + (size_t)tq * 2 * a.C;
-                    sl.store(pt, a.C, lg);
-                    sh.store(pt + a.C, a.C, lg);
-                } else {
-                    acm_finish<VEC, G, R>(a, seg, deg, lg, sl, sh);
-                }
-            }
-        }
-    } else {
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        if (slot < a.N) {
-            const int seg = a.perm[slot];
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            acm_gather<VEC, G, R>(a, seg, qs, 0, deg, 1, 0, lg, sl, sh);
-            acm_finish<VEC, G, R>(a, seg, deg, lg, sl, sh);
-        }
-    }
-}
-
-__device__ __forceinline__ float acm_wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
+    using Sums = AcmSums<VEC, G, R>;
+    Sums acc;
+    walk_rows<G>(
+        a, blockIdx.x, a.N, acc,
+        [&](int seg, int qs, int e0, int e1, int stride, int first, int lg, Sums &s) {
+            acm_gather<VEC, G, R>(a, seg, qs, e0, e1, stride, first, lg, s.l, s.h);
+        },
+        [&](int tq, int lg, Sums &s) {
+            float *pt = a.partial + (size_t)tq * 2 * a.C;
+            s.l.store(pt, a.C, lg);
+            s.h.store(pt + a.C, a.C, lg);
+        },
+        [&](int seg, int deg, int lg, Sums &s) { acm_finish<VEC, G, R>(a, seg, deg, lg, s.l, s.h); });
 }
 
 // split rows: the sum of the tasks' partial rows in a fixed order, then the epilogue of acm_finish with one channel
@@ -259,7 +225,7 @@ static __global__ __launch_bounds__(256) void k_acm_fin(const AcmArgs a)
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float v = acm_wave_sum(pd[k]);
+        const float v = wave_sum_f(pd[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();
@@ -454,12 +420,9 @@ static __global__ __launch_bounds__(256) void k_acm_params(const double *__restr
 
 template <int VEC, int G, int R> int launch_acm(const AcmArgs &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     AcmArgs a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
-    if (a.nbA + a.nbB + nbC > 0) k_acm<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    const int grid = plan_side(a, a.N, 64 / G);
+    if (grid > 0) k_acm<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_acm_fin<<<a.n_split, 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
@@ -492,7 +455,7 @@ struct AcmLayout { int64_t gp, parts, total; };       // the task partials are i
 static AcmLayout acm_layout(const sngnn_graph_t *g, int C)
 {
     AcmLayout L;
-    L.gp = up256((int64_t)std::max(g->n_tasks, g->n_stasks) * 2 * C * 4);
+    L.gp = task_partial_bytes(g, 2 * C);
     L.parts = L.gp + up256(g->N * (int64_t)2 * C * 4);
     L.total = L.parts + up256((int64_t)(3 * C + 9) * ACM_PARAM_BLOCKS * 8);
     return L;

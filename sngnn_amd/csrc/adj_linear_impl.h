@@ -6,11 +6,11 @@
 // operand is one contiguous row.  Same degree classes and fixed summation order
 // as the aggregation kernels; no atomics.
 #pragma once
-#include "device_utils.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
-struct AdjArgs {
+struct AdjArgs : RowSide {      // segments (CSR or CSC), gathered ids, degree order: row_walk.h
     const float *table;         // rows to gather  [N, C]
     const float *w;             // per-entry weights in SEGMENT order (w[ptr[seg] + t]) or nullptr = 1 (weighted gather-sum:
                                 // GGCNlayer_SP's plain propagation, models.py:1544-1549)
@@ -18,40 +18,9 @@ struct AdjArgs {
     float *out;                 // [N, C]
     float *partial;             // [n_tasks, C]
     int C, N;
-    const int32_t *ptr, *idx, *perm;    // segments (CSR or CSC), gathered ids, degree order
     int seg_shift;              // output row r reads segment r + seg_shift
     int idx_shift;              // gathered row = idx[q] + idx_shift
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
 };
-
-template <int VEC, int G, int R>
-__device__ __forceinline__ void adj_gather(const AdjArgs &a, int qs, int e0, int e1, int stride,
-                                           int first, int lg, Row<VEC, G, R> &acc)
-{
-    using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        bool act[U];
-        float wv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] + a.idx_shift : 0;
-            wv[u] = (a.w && act[u]) ? a.w[qs + t] : 1.0f;         // (uniform pointer test; travels with the row)
-            x[u].load(a.table + (size_t)row * a.C, a.C, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) {
-                if (a.w) acc.axpy(wv[u], x[u]);                    // value * row rounded, then added (a sparse mm's order)
-                else acc.add(x[u]);
-            }
-    }
-}
 
 template <int VEC, int G, int R>
 __device__ __forceinline__ void adj_finish(const AdjArgs &a, int r, int lg, Row<VEC, G, R> &acc)
@@ -65,53 +34,26 @@ __device__ __forceinline__ void adj_finish(const AdjArgs &a, int r, int lg, Row<
     acc.store(a.out + (size_t)r * a.C, a.C, lg);
 }
 
+// the gather-sum of table rows (value * row rounded, then added, where there are weights: a sparse mm's order), then
+// adj_finish for the segments that have an output row
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_adj(const AdjArgs a)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
-    const int b = blockIdx.x;
     RowT acc;
-    acc.zero();
-    if (b < a.nbA + a.nbB) {
-        // split task or one wave per segment
-        const bool task = b < a.nbA;
-        int seg, e0, tq = 0;
-        if (task) {
-            tq = b * WAVES + wave;
-            if (tq >= a.n_tasks) return;
-            seg = a.perm[a.task_slot[tq]];
-            e0 = a.task_chunk[tq] * CHUNK;
-        } else {
-            const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-            if (slot >= a.n_med_end) return;
-            seg = a.perm[slot];
-            e0 = 0;
-        }
-        const int qs = a.ptr[seg];
-        const int deg = a.ptr[seg + 1] - qs;
-        const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-        adj_gather<VEC, G, R>(a, qs, e0, e1, NG, gid, lg, acc);
-        acc.reduce_across_groups();
-        if (gid != 0) return;
-        if (task) acc.store(a.partial + (size_t)tq * a.C, a.C, lg);
-        else if (seg - a.seg_shift >= 0) adj_finish<VEC, G, R>(a, seg - a.seg_shift, lg, acc);
-    } else {
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        if (slot >= a.N) return;
-        const int seg = a.perm[slot];
-        const int qs = a.ptr[seg];
-        const int deg = a.ptr[seg + 1] - qs;
-        adj_gather<VEC, G, R>(a, qs, 0, deg, 1, 0, lg, acc);
-        if (seg - a.seg_shift >= 0) adj_finish<VEC, G, R>(a, seg - a.seg_shift, lg, acc);
-    }
+    walk_rows<G>(
+        a, blockIdx.x, a.N, acc,
+        [&](int, int qs, int e0, int e1, int stride, int first, int lg, RowT &s) {
+            gather_rows<VEC, G, R, gather_unroll(R)>(a.table, a.C, a.C, a.idx, qs, e0, e1, stride, first, lg, s,
+                                                     EntryWeight{a.w}, a.idx_shift);
+        },
+        [&](int tq, int lg, RowT &s) { s.store(a.partial + (size_t)tq * a.C, a.C, lg); },
+        [&](int seg, int, int lg, RowT &s) {
+            if (seg - a.seg_shift >= 0) adj_finish<VEC, G, R>(a, seg - a.seg_shift, lg, s);
+        });
 }
 
-// split segments: the sum of the tasks' partial rows (+ bias).  Thread (c, q) adds every
-// 4th task in four independent chains (the loads of a hub's ~100 tasks overlap); the sums
-// are combined in fixed order (deterministic).
+// split segments: the sum of the tasks' partial rows (+ bias)
 static __global__ __launch_bounds__(256) void k_adj_fin(const AdjArgs a)
 {
     __shared__ float s[4][64];
@@ -123,21 +65,8 @@ static __global__ __launch_bounds__(256) void k_adj_fin(const AdjArgs a)
     const int cl = threadIdx.x & 63, q = threadIdx.x >> 6;
     for (int c0 = 0; c0 < a.C; c0 += 64) {
         const int c = c0 + cl;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        if (c < a.C) {
-            int t = t0 + q;
-            for (; t + 12 < t1; t += 16) {
-                v0 += a.partial[(size_t)t * a.C + c];
-                v1 += a.partial[(size_t)(t + 4) * a.C + c];
-                v2 += a.partial[(size_t)(t + 8) * a.C + c];
-                v3 += a.partial[(size_t)(t + 12) * a.C + c];
-            }
-            for (; t < t1; t += 4) v0 += a.partial[(size_t)t * a.C + c];
-        }
-        s[q][cl] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
-        if (q == 0 && c < a.C)
-            a.out[(size_t)r * a.C + c] = ((s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl])) + (a.bias ? a.bias[c] : 0.f);
+        const float sum = combine_task_sums(s, sum_task_partials(a.partial, a.C, t0, t1, c, q), q, cl);
+        if (q == 0 && c < a.C) a.out[(size_t)r * a.C + c] = sum + (a.bias ? a.bias[c] : 0.f);
         __syncthreads();
     }
 }
@@ -189,12 +118,9 @@ int launch_pair_dot(const float *A, const int32_t *ia, const float *B, const int
 
 template <int VEC, int G, int R> int launch_adj(const AdjArgs &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     AdjArgs a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
-    if (a.nbA + a.nbB + nbC > 0) k_adj<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    const int grid = plan_side(a, a.N, 64 / G);
+    if (grid > 0) k_adj<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_adj_fin<<<a.n_split, 256, 0, st>>>(a);
     if (a.seg_shift > 0) k_adj_tail<<<std::min(1024, ceil_div((int64_t)a.seg_shift * a.C, 256)), 256, 0, st>>>(a, a.N - a.seg_shift);
     SN_HIP(hipGetLastError());

@@ -56,6 +56,21 @@ __device__ __forceinline__ int wave_sum_i(int v)
     return v;
 }
 
+// the same tree (partners 32, 16, ... 1 lanes away) on floats and doubles: every lane ends with the same bits
+__device__ __forceinline__ float wave_sum_f(float v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
 // Orders LDS traffic between the lanes of ONE wave (DS ops of a wave execute in
 // issue order; the fences stop the compiler from moving LDS accesses across).  The
 // fences name the LDS address space only: an all-address-space fence would also drain

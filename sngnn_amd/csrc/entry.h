@@ -119,6 +119,37 @@ template <typename F> int dispatch_vec(const RowCfg &cfg, F &&f)
     }
 }
 
+// f(VEC, G, R as integral constants) for a hop on a column slice: the lane layouts are row_cfg(W)'s, and - where the
+// slice's alignment forces a narrower vector than W's own - the same groups with 2 or 4 times the steps
+template <typename F> int dispatch_slice_layout(int vec, int g, int r, F &&f)
+{
+    using std::integral_constant;
+    return dispatch_vec(RowCfg{vec, g, r}, [&](auto v) {
+        constexpr int VEC = decltype(v)::value;
+#define SN_GR_CASE(G_, R_) case G_ * 100 + R_: return f(v, integral_constant<int, G_>{}, integral_constant<int, R_>{});
+        switch (g * 100 + r) {
+            SN_GR_CASE(8, 1) SN_GR_CASE(16, 1) SN_GR_CASE(32, 1) SN_GR_CASE(64, 1) SN_GR_CASE(64, 2) SN_GR_CASE(64, 4)
+            SN_GR_CASE(64, 8)
+        default: break;
+        }
+        if constexpr (VEC < 4) {
+            switch (g * 100 + r) {
+                SN_GR_CASE(8, 2) SN_GR_CASE(16, 2) SN_GR_CASE(32, 2)
+            default: break;
+            }
+        }
+        if constexpr (VEC == 1) {
+            switch (g * 100 + r) {
+                SN_GR_CASE(8, 4) SN_GR_CASE(16, 4) SN_GR_CASE(32, 4)
+            default: break;
+            }
+        }
+#undef SN_GR_CASE
+        set_error("unsupported channel layout");
+        return (int)SNGNN_EINVAL;
+    });
+}
+
 // f(Storage<S>, std::integral_constant<int, VEC>): the runtime pair (cfg.vec, dtype) as a compile-time pair.  The
 // launchers `template <typename S, int VEC> int launch_..._vec(const RowCfg &, ...)` of the *_impl.h headers are
 // defined one per translation unit (family x storage type x vector width); SNGNN_LAUNCH_VEC names one by family.

@@ -2,9 +2,9 @@
 //     A^ = D^-1/2 (A + I) D^-1/2     (prop.hip's adjacency: deg_i = in-degree with the loop, dinv = deg^-1/2)
 // on a COLUMN SLICE of a wider table, with a split store:
 //     z_i = dinv_i S_i,  S_i = sum_{e -> i} dinv_src src[src, 0 .. W)
-// k_gcn2_hop's skeleton (small rows by lane group, medium rows by wave, hubs as 128-edge tasks + a finalize; the rows
-// gathered UNSCALED and multiplied by dinv[src], which is loaded next to the column id; fixed summation order, no
-// atomics; every product and sum rounded separately: -ffp-contract=off).  New here:
+// The row-class walk of row_walk.h (small rows by lane group, medium rows by wave, hubs as 128-edge tasks + a finalize;
+// the rows gathered UNSCALED and multiplied by dinv[src], which is loaded next to the column id; fixed summation order,
+// no atomics; every product and sum rounded separately: -ffp-contract=off).  New here:
 //   strided rows   source and destinations are W columns of tables with their own row strides
 //   split store    the first W0 columns of z go to dst0 (with the epilogue: + bias, the running-statistics norm, relu),
 //                  the other W - W0 to dst1.  MixHop's launch j gathers the hops - j + 1 slices that still need
@@ -18,14 +18,14 @@
 // table gives the bits of the dense call.
 #include <algorithm>
 
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
 constexpr int COLSUM_BLOCKS = 1024;          // partial column sums of sngnn_gcn_bias_grad
 
-struct GcnArgs {
+struct GcnArgs : RowSide {
     const float *src;            // column 0 of the gathered slice
     float *dst0, *dst1;
     const float *pass_src;
@@ -36,39 +36,7 @@ struct GcnArgs {
     const float *dinv;           // [N]
     float *partial;              // [n_tasks, W]
     int N;
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
 };
-
-// acc += dinv[src] * src[src, 0 .. W) over the edges e0 + first, + stride, ... < e1 of the segment at qs
-template <int VEC, int G, int R>
-__device__ __forceinline__ void gcn_gather(const GcnArgs &a, int qs, int e0, int e1, int stride, int first, int lg,
-                                           Row<VEC, G, R> &acc)
-{
-    using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        float w[U];
-        bool act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] : 0;
-            w[u] = a.dinv[row];
-            x[u].load(a.src + (size_t)row * a.ld_src, a.W, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) {
-                x[u].scale(w[u]);
-                acc.add(x[u]);
-            }
-    }
-}
 
 // the epilogue of one dst0 element (column c < W0)
 __device__ __forceinline__ float gcn_epilogue(const GcnArgs &a, int c, float z)
@@ -112,49 +80,24 @@ __device__ __forceinline__ void gcn_finish(const GcnArgs &a, int r, int lg, Row<
     }
 }
 
+// S_i = sum dinv[src] * src[src, 0 .. W) (gather_rows), then gcn_finish
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_gcn_hop(const GcnArgs a)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
-    const int b = blockIdx.x;
     RowT acc;
-    acc.zero();
-    if (b < a.nbA + a.nbB) {
-        // split task or one wave per segment
-        const bool task = b < a.nbA;
-        const int tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        const bool live = task ? tq < a.n_tasks : slot < a.n_med_end;          // (wave-uniform)
-        if (live) {
-            const int seg = a.perm[task ? a.task_slot[tq] : slot];
-            const int e0 = task ? a.task_chunk[tq] * CHUNK : 0;
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            gcn_gather<VEC, G, R>(a, qs, e0, e1, NG, gid, lg, acc);
-            acc.reduce_across_groups();
-            if (gid == 0) {
-                if (task) acc.store(a.partial + (size_t)tq * a.W, a.W, lg);
-                else gcn_finish<VEC, G, R>(a, seg, lg, acc);
-            }
-        }
-    } else {
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        if (slot < a.N) {
-            const int seg = a.perm[slot];
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            gcn_gather<VEC, G, R>(a, qs, 0, deg, 1, 0, lg, acc);
-            gcn_finish<VEC, G, R>(a, seg, lg, acc);
-        }
-    }
+    walk_rows<G>(
+        a, blockIdx.x, a.N, acc,
+        [&](int, int qs, int e0, int e1, int stride, int first, int lg, RowT &s) {
+            gather_rows<VEC, G, R, gather_unroll(R)>(a.src, a.ld_src, a.W, a.idx, qs, e0, e1, stride, first, lg, s,
+                                                     RowWeight{a.dinv});
+        },
+        [&](int tq, int lg, RowT &s) { s.store(a.partial + (size_t)tq * a.W, a.W, lg); },
+        [&](int seg, int, int lg, RowT &s) { gcn_finish<VEC, G, R>(a, seg, lg, s); });
 }
 
-// split segments: the sum of the tasks' partial rows in k_adj_fin's order, then gcn_finish's arithmetic per element
-// and the row's pass-through copy
+// split segments: the sum of the tasks' partial rows, then gcn_finish's arithmetic per element and the row's
+// pass-through copy
 static __global__ __launch_bounds__(256) void k_gcn_hop_fin(const GcnArgs a)
 {
     __shared__ float s[4][64];
@@ -165,21 +108,9 @@ static __global__ __launch_bounds__(256) void k_gcn_hop_fin(const GcnArgs a)
     const float di = a.dinv[r];
     for (int c0 = 0; c0 < a.W; c0 += 64) {
         const int c = c0 + cl;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        if (c < a.W) {
-            int t = t0 + q;
-            for (; t + 12 < t1; t += 16) {
-                v0 += a.partial[(size_t)t * a.W + c];
-                v1 += a.partial[(size_t)(t + 4) * a.W + c];
-                v2 += a.partial[(size_t)(t + 8) * a.W + c];
-                v3 += a.partial[(size_t)(t + 12) * a.W + c];
-            }
-            for (; t < t1; t += 4) v0 += a.partial[(size_t)t * a.W + c];
-        }
-        s[q][cl] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
+        const float sum = combine_task_sums(s, sum_task_partials(a.partial, a.W, t0, t1, c, q), q, cl);
         if (q == 0 && c < a.W) {
-            const float z = ((s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl])) * di;
+            const float z = sum * di;
             if (c < a.W0) a.dst0[(size_t)r * a.ld0 + c] = gcn_epilogue(a, c, z);
             else a.dst1[(size_t)r * a.ld1 + (c - a.W0)] = z;
         }
@@ -190,40 +121,12 @@ static __global__ __launch_bounds__(256) void k_gcn_hop_fin(const GcnArgs a)
 
 template <int VEC, int G, int R> int launch_gcn_hop(const GcnArgs &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     GcnArgs a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
-    if (a.nbA + a.nbB + nbC > 0) k_gcn_hop<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    const int grid = plan_side(a, a.N, 64 / G);
+    if (grid > 0) k_gcn_hop<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_gcn_hop_fin<<<a.n_split, 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
-}
-
-// (G, R) of the layouts a hop can take: row_cfg(W)'s, and its groups with 2 or 4 times the steps
-template <int VEC> static int dispatch_gcn_hop_gr(int g, int r, const GcnArgs &a, hipStream_t st)
-{
-#define GCN_CASE(G_, R_) case G_ * 100 + R_: return launch_gcn_hop<VEC, G_, R_>(a, st);
-    switch (g * 100 + r) {
-        GCN_CASE(8, 1) GCN_CASE(16, 1) GCN_CASE(32, 1) GCN_CASE(64, 1) GCN_CASE(64, 2) GCN_CASE(64, 4) GCN_CASE(64, 8)
-    default: break;
-    }
-    if constexpr (VEC < 4) {
-        switch (g * 100 + r) {
-            GCN_CASE(8, 2) GCN_CASE(16, 2) GCN_CASE(32, 2)
-        default: break;
-        }
-    }
-    if constexpr (VEC == 1) {
-        switch (g * 100 + r) {
-            GCN_CASE(8, 4) GCN_CASE(16, 4) GCN_CASE(32, 4)
-        default: break;
-        }
-    }
-#undef GCN_CASE
-    set_error("unsupported channel layout");
-    return SNGNN_EINVAL;
 }
 
 // the vector width of a call: the largest of 4, 2, 1 that divides every width, every stride and every table
@@ -294,11 +197,6 @@ static __global__ __launch_bounds__(1024) void k_gcn_colsum_fin(const double *__
     }
 }
 
-static int64_t gcn_partial_bytes(const sngnn_graph_t *g, int W)
-{
-    return up256((int64_t)std::max(g->n_tasks, g->n_stasks) * W * 4) + 256;
-}
-
 }  // namespace sngnn
 
 using namespace sngnn;
@@ -307,7 +205,7 @@ extern "C" int64_t sngnn_gcn_workspace_bytes(const sngnn_graph_t *g, int W)
 {
     RowCfg cfg;
     if (g == nullptr || !row_cfg(W, cfg)) return 0;
-    return std::max<int64_t>(gcn_partial_bytes(g, W), (int64_t)COLSUM_BLOCKS * W * 8);
+    return std::max<int64_t>(task_partial_bytes(g, W) + 256, (int64_t)COLSUM_BLOCKS * W * 8);
 }
 
 extern "C" int sngnn_gcn_hop(const sngnn_graph_t *g, const sngnn_gcn_hop_t *h, const float *dinv, int transpose,
@@ -357,12 +255,9 @@ extern "C" int sngnn_gcn_hop(const sngnn_graph_t *g, const sngnn_gcn_hop_t *h, c
     q.bias = h->bias; q.rm = h->rm; q.invstd = h->invstd; q.gamma = h->gamma; q.beta = h->beta_bn;
     q.dinv = dinv;
     q.partial = (float *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    switch (vec) {
-    case 4: return dispatch_gcn_hop_gr<4>(cfg.g, r, q, st);
-    case 2: return dispatch_gcn_hop_gr<2>(cfg.g, r, q, st);
-    default: return dispatch_gcn_hop_gr<1>(cfg.g, r, q, st);
-    }
+    return dispatch_slice_layout(vec, cfg.g, r, [&](auto v, auto g_, auto r_) {
+        return launch_gcn_hop<decltype(v)::value, decltype(g_)::value, decltype(r_)::value>(q, (hipStream_t)stream);
+    });
 }
 
 extern "C" int sngnn_gcn_bias_grad(const float *g, int64_t N, int C, float *grad_bias, void *workspace, void *stream)

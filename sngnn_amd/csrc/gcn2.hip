@@ -5,7 +5,7 @@
 //   hop   (A^ x)_i = dinv_i S_i,  S_i = sum_{e -> i} dinv_src x_src.  The rows of x are gathered UNSCALED and multiplied
 //         by dinv[src], which is loaded next to the column id: 4 more bytes per edge (from a 4 N byte table that stays
 //         in cache) instead of the read and the write of a scaled copy of x that prop.hip's iterate would cost per
-//         layer.  Skeleton of adj_linear_impl.h / prop.hip: small rows by lane group, medium rows by wave, hubs as
+//         layer.  The row-class walk of row_walk.h: small rows by lane group, medium rows by wave, hubs as
 //         128-edge tasks + a finalize; fixed summation order, no atomics.  Store epilogue: s_i = a (dinv_i S_i) + b x0_i.
 //         Every product and sum is rounded separately (-ffp-contract=off).  On the CSC side the same kernel is A^T.
 //   map   out = c0 s + c1 (s W): s streamed once in 32-row tiles through LDS, W resident in LDS for the workgroup's
@@ -16,12 +16,12 @@
 // inside a lane group would run from LDS at about the cost of the read it saves (an estimate).
 #include <algorithm>
 
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
-struct Gcn2Args {
+struct Gcn2Args : RowSide {
     const float *x;             // rows to gather  [N, C]
     const float *x0;            // [N, C] or nullptr: the b x0 term
     const float *dinv;          // [N]
@@ -29,40 +29,7 @@ struct Gcn2Args {
     float *out;                 // [N, C]
     float *partial;             // [n_tasks, C]
     int C, N;
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
 };
-
-// acc += dinv[src] * x[src] over the edges e0 + first, + stride, ... < e1 of the segment at qs (product rounded, then
-// the sum: -ffp-contract=off)
-template <int VEC, int G, int R>
-__device__ __forceinline__ void gcn2_gather(const Gcn2Args &a, int qs, int e0, int e1, int stride, int first, int lg,
-                                            Row<VEC, G, R> &acc)
-{
-    using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        float w[U];
-        bool act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] : 0;
-            w[u] = a.dinv[row];
-            x[u].load(a.x + (size_t)row * a.C, a.C, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) {
-                x[u].scale(w[u]);
-                acc.add(x[u]);
-            }
-    }
-}
 
 // the epilogue of row r from its gathered sum s
 template <int VEC, int G, int R>
@@ -80,48 +47,23 @@ __device__ __forceinline__ void gcn2_finish(const Gcn2Args &a, int r, int lg, Ro
     s.store(a.out + off, a.C, lg);
 }
 
+// S_i = sum dinv[src] * x[src] (gather_rows), then gcn2_finish
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_gcn2_hop(const Gcn2Args a)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
-    const int b = blockIdx.x;
     RowT acc;
-    acc.zero();
-    if (b < a.nbA + a.nbB) {
-        // split task or one wave per segment
-        const bool task = b < a.nbA;
-        const int tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        const bool live = task ? tq < a.n_tasks : slot < a.n_med_end;          // (wave-uniform)
-        if (live) {
-            const int seg = a.perm[task ? a.task_slot[tq] : slot];
-            const int e0 = task ? a.task_chunk[tq] * CHUNK : 0;
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            gcn2_gather<VEC, G, R>(a, qs, e0, e1, NG, gid, lg, acc);
-            acc.reduce_across_groups();
-            if (gid == 0) {
-                if (task) acc.store(a.partial + (size_t)tq * a.C, a.C, lg);
-                else gcn2_finish<VEC, G, R>(a, seg, lg, acc);
-            }
-        }
-    } else {
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        if (slot < a.N) {
-            const int seg = a.perm[slot];
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            gcn2_gather<VEC, G, R>(a, qs, 0, deg, 1, 0, lg, acc);
-            gcn2_finish<VEC, G, R>(a, seg, lg, acc);
-        }
-    }
+    walk_rows<G>(
+        a, blockIdx.x, a.N, acc,
+        [&](int, int qs, int e0, int e1, int stride, int first, int lg, RowT &s) {
+            gather_rows<VEC, G, R, gather_unroll(R)>(a.x, a.C, a.C, a.idx, qs, e0, e1, stride, first, lg, s,
+                                                     RowWeight{a.dinv});
+        },
+        [&](int tq, int lg, RowT &s) { s.store(a.partial + (size_t)tq * a.C, a.C, lg); },
+        [&](int seg, int, int lg, RowT &s) { gcn2_finish<VEC, G, R>(a, seg, lg, s); });
 }
 
-// split segments: the sum of the tasks' partial rows in k_adj_fin's order, then gcn2_finish's arithmetic per element
+// split segments: the sum of the tasks' partial rows, then gcn2_finish's arithmetic per element
 static __global__ __launch_bounds__(256) void k_gcn2_hop_fin(const Gcn2Args a)
 {
     __shared__ float s[4][64];
@@ -132,22 +74,10 @@ static __global__ __launch_bounds__(256) void k_gcn2_hop_fin(const Gcn2Args a)
     const float di = a.dinv[r];
     for (int c0 = 0; c0 < a.C; c0 += 64) {
         const int c = c0 + cl;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        if (c < a.C) {
-            int t = t0 + q;
-            for (; t + 12 < t1; t += 16) {
-                v0 += a.partial[(size_t)t * a.C + c];
-                v1 += a.partial[(size_t)(t + 4) * a.C + c];
-                v2 += a.partial[(size_t)(t + 8) * a.C + c];
-                v3 += a.partial[(size_t)(t + 12) * a.C + c];
-            }
-            for (; t < t1; t += 4) v0 += a.partial[(size_t)t * a.C + c];
-        }
-        s[q][cl] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
+        const float sum = combine_task_sums(s, sum_task_partials(a.partial, a.C, t0, t1, c, q), q, cl);
         if (q == 0 && c < a.C) {
             const size_t at = (size_t)r * a.C + c;
-            float z = (((s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl])) * di) * a.a;
+            float z = (sum * di) * a.a;
             if (a.x0) z = z + a.x0[at] * a.b;
             a.out[at] = z;
         }
@@ -157,12 +87,9 @@ static __global__ __launch_bounds__(256) void k_gcn2_hop_fin(const Gcn2Args a)
 
 template <int VEC, int G, int R> int launch_gcn2_hop(const Gcn2Args &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     Gcn2Args a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
-    if (a.nbA + a.nbB + nbC > 0) k_gcn2_hop<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
+    const int grid = plan_side(a, a.N, 64 / G);
+    if (grid > 0) k_gcn2_hop<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_gcn2_hop_fin<<<a.n_split, 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
@@ -272,11 +199,6 @@ static int launch_gcn2_map(const float *s, const float *w, float c0, float c1, i
     return SNGNN_OK;
 }
 
-static int64_t gcn2_partial_bytes(const sngnn_graph_t *g, int C)
-{
-    return up256((int64_t)std::max(g->n_tasks, g->n_stasks) * C * 4) + 256;
-}
-
 }  // namespace sngnn
 
 using namespace sngnn;
@@ -285,7 +207,7 @@ extern "C" int64_t sngnn_gcn2_workspace_bytes(const sngnn_graph_t *g, int C)
 {
     RowCfg cfg;
     if (g == nullptr || !row_cfg(C, cfg)) return 0;
-    return gcn2_partial_bytes(g, C);
+    return task_partial_bytes(g, C) + 256;
 }
 
 extern "C" int sngnn_gcn2_hop(const sngnn_graph_t *g, const float *x, const float *x0, const float *dinv, float a, float b,

@@ -12,7 +12,7 @@
 //           (the backward's gT and gM).
 //   solve   one workgroup, double: in-place Gauss-Jordan without pivoting (the matrix is SPD with smallest eigenvalue
 //           >= coe2^2), then M, T and W = G V.  Its backward takes gM, gT to gG + gG^T and grad_diag.
-//   hops    unweighted row gather-sums on the row classes of adj_linear_impl.h / prop.hip (lane group, wave, 128-entry
+//   hops    unweighted row gather-sums on the row-class walk of row_walk.h (lane group, wave, 128-entry
 //           tasks + a finalize; fixed order, no atomics).  Forward: t_k = A t_{k-1}, S += w_k t_k in the stores, the mix
 //           above in the last hop's store (M, T in LDS, the C x C products per row accumulated in double).  Backward:
 //           a row-local pass forms q = beta g M^T, grad_h0 and coe1 g T^T; r_k = A^T r_{k-1}, grad_x += w_k r_k in the
@@ -20,8 +20,8 @@
 // Every fp32 product and sum is rounded separately (-ffp-contract=off).  Nothing synchronises with the host.
 #include <algorithm>
 
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
@@ -31,13 +31,6 @@ constexpr int GRAM_TILE = 32;
 constexpr int GRAM_BLOCKS = 256;
 constexpr int GRAM_EPT = GLO_CC / 256;             // elements of the product a thread owns at most
 constexpr int GLO_PRE_BLOCKS = 2048;
-
-__device__ __forceinline__ double glo_wave_sum_d(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // ---- gram ---------------------------------------------------------------------------------------------------------------
 struct GramArgs {
@@ -252,7 +245,7 @@ static __global__ __launch_bounds__(256) void k_glo_solve_bwd(const SolveBwdArgs
 }
 
 // ---- hops ---------------------------------------------------------------------------------------------------------------
-struct GloArgs {
+struct GloArgs : RowSide {
     const float *t;             // iterate to gather [N, C]
     const float *x;             // forward: S's first term and the mix; backward: the dots and the last fold
     const float *h0;            // forward, last hop
@@ -267,33 +260,7 @@ struct GloArgs {
     double beta, gamma, coe1;
     float *partial;             // [n_tasks, C]
     int C, N;
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
 };
-
-template <int VEC, int G>
-__device__ __forceinline__ void glo_gather(const GloArgs &a, int qs, int e0, int e1, int stride, int first, int lg,
-                                           Row<VEC, G, 1> &acc)
-{
-    using RowT = Row<VEC, G, 1>;
-    constexpr int U = 4;
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        bool act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] : 0;
-            x[u].load(a.t + (size_t)row * a.C, a.C, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) acc.add(x[u]);
-    }
-}
 
 // forward epilogue of row r from its gathered sum s (= t_k's row); su / ss: this lane group's staging rows in LDS
 template <int VEC, int G>
@@ -390,6 +357,8 @@ __device__ __forceinline__ double glo_finish_bwd(const GloArgs &a, int r, int lg
     return d;
 }
 
+// The body below is row_walk.h's walk_rows, spelled out: through the template, k_glo_hop<4, 64, false> takes 74 VGPRs
+// instead of 72 and loses a wave per SIMD (7 -> 6).  The gather, the finalize sum and the launch plan are the shared ones.
 template <int VEC, int G, bool BWD>
 __global__ __launch_bounds__(BLOCK) void k_glo_hop(const GloArgs a)
 {
@@ -440,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void k_glo_hop(const GloArgs a)
             const int qs = a.ptr[seg];
             const int deg = a.ptr[seg + 1] - qs;
             const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            glo_gather<VEC, G>(a, qs, e0, e1, NG, gid, lg, acc);
+            gather_rows<VEC, G, 1, 4>(a.t, a.C, a.C, a.idx, qs, e0, e1, NG, gid, lg, acc, NoWeight{});
             acc.reduce_across_groups();
             if (gid == 0) {
                 if (task) acc.store(a.partial + (size_t)tq * a.C, a.C, lg);
@@ -453,19 +422,19 @@ __global__ __launch_bounds__(BLOCK) void k_glo_hop(const GloArgs a)
             const int seg = a.perm[slot];
             const int qs = a.ptr[seg];
             const int deg = a.ptr[seg + 1] - qs;
-            glo_gather<VEC, G>(a, qs, 0, deg, 1, 0, lg, acc);
+            gather_rows<VEC, G, 1, 4>(a.t, a.C, a.C, a.idx, qs, 0, deg, 1, 0, lg, acc, NoWeight{});
             d = finish(seg, acc);
         }
     }
     if (BWD && a.dotpart && b >= a.nbA) {              // (block-uniform) the workgroup's partial dot, fixed order
-        d = glo_wave_sum_d(d);
+        d = wave_sum_d(d);
         if (lane == 0) sd[wave] = d;
         __syncthreads();
         if (threadIdx.x == 0) a.dotpart[b - a.nbA] = (sd[0] + sd[1]) + (sd[2] + sd[3]);
     }
 }
 
-// split segments: the sum of the tasks' partial rows in k_adj_fin's order, then the epilogue per element (the
+// split segments: the sum of the tasks' partial rows, then the epilogue per element (the
 // arithmetic of glo_finish_*; the matrices from global memory: there are few such rows); the row's dot is partial
 // number part0 + p
 static __global__ __launch_bounds__(256) void k_glo_fin(const GloArgs a, int bwd, int part0)
@@ -480,20 +449,7 @@ static __global__ __launch_bounds__(256) void k_glo_fin(const GloArgs a, int bwd
     const int C = a.C;
     const bool mine = q == 0 && c < C;
     const size_t at = (size_t)r * C + (c < C ? c : 0);
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-    if (c < C) {
-        int t = t0 + q;
-        for (; t + 12 < t1; t += 16) {
-            v0 += a.partial[(size_t)t * C + c];
-            v1 += a.partial[(size_t)(t + 4) * C + c];
-            v2 += a.partial[(size_t)(t + 8) * C + c];
-            v3 += a.partial[(size_t)(t + 12) * C + c];
-        }
-        for (; t < t1; t += 4) v0 += a.partial[(size_t)t * C + c];
-    }
-    s[q][c] = (v0 + v1) + (v2 + v3);
-    __syncthreads();
-    const float z = (s[0][c] + s[1][c]) + (s[2][c] + s[3][c]);
+    const float z = combine_task_sums(s, sum_task_partials(a.partial, C, t0, t1, c, q), q, c);
     float accv = 0.f, xv = 0.f, hv = 0.f;
     double d = 0.0;
     if (mine) {
@@ -535,7 +491,7 @@ static __global__ __launch_bounds__(256) void k_glo_fin(const GloArgs a, int bwd
         }
     }
     if (bwd && a.dotpart && q == 0) {                  // (wave 0 holds the row's elements)
-        d = glo_wave_sum_d(d);
+        d = wave_sum_d(d);
         if (c == 0) a.dotpart[part0 + p] = d;
     }
 }
@@ -602,13 +558,11 @@ template <int VEC, int G, bool BWD> int launch_glo(const GloArgs &a0, hipStream_
 {
     constexpr int NG = 64 / G;
     GloArgs a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
+    const int grid = plan_side(a, a.N, NG);
     const bool last = BWD ? a.G2 != nullptr : a.out != nullptr;
     const size_t lds = !last ? 0 : (size_t)a.C * a.C * 8 + (BWD ? 0 : WAVES * NG * GLO_MAX_C * 8) + WAVES * NG * GLO_MAX_C * 4;
-    if (a.nbA + a.nbB + nbC > 0) k_glo_hop<VEC, G, BWD><<<a.nbA + a.nbB + nbC, BLOCK, lds, st>>>(a);
-    if (a.n_split > 0) k_glo_fin<<<a.n_split, 256, 0, st>>>(a, BWD ? 1 : 0, a.nbB + nbC);
+    if (grid > 0) k_glo_hop<VEC, G, BWD><<<grid, BLOCK, lds, st>>>(a);
+    if (a.n_split > 0) k_glo_fin<<<a.n_split, 256, 0, st>>>(a, BWD ? 1 : 0, grid - a.nbA);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -640,8 +594,7 @@ static int glo_parts(const sngnn_graph_t *g, bool transpose, const RowCfg &cfg)
 {
     GloArgs a;
     glo_side(g, transpose, a);
-    return ceil_div(a.n_med_end - a.n_split, WAVES) + ceil_div(a.N - a.n_med_end, (int64_t)WAVES * (64 / cfg.g)) +
-           a.n_split;
+    return plan_side(a, a.N, 64 / cfg.g) - a.nbA + a.n_split;
 }
 
 static int64_t gram_bytes(int C) { return up256((int64_t)GRAM_BLOCKS * 2 * C * C * 8); }
@@ -655,7 +608,7 @@ static GloLayout glo_layout(const sngnn_graph_t *g, int C, int K, const RowCfg &
     L.u0 = gram_bytes(C);                              // (the gram partials come first: sngnn_glognn_gram's workspace)
     L.u1 = L.u0 + rows;
     L.partial = L.u1 + rows;
-    L.dots = L.partial + up256((int64_t)std::max(g->n_tasks, g->n_stasks) * C * 4);
+    L.dots = L.partial + task_partial_bytes(g, C);
     L.stride = std::max<int64_t>(1, glo_parts(g, true, cfg));
     L.total = L.dots + up256((int64_t)std::max(K, 1) * L.stride * 8);
     return L;

@@ -11,14 +11,14 @@
 //                                         row's own bit cleared), read in word order - the row comes out sorted
 //    Count and fill are separate launches with the caller's scan in between; no workgroup waits for another.
 // 2. The hop.  z = [A^1 x | A^2 x] with A^s = D_s^-1/2 A_s D_s^-1/2, D_s the ROW (in-)degree of A_s on both sides and
-//    dinv = 0 for an empty row.  k_gcn_hop's skeleton (small rows by lane group, medium rows by wave, hubs as 128-edge
-//    tasks + a finalize; rows gathered unscaled and multiplied by dinv[src]; fixed order, no floating-point atomics;
-//    -ffp-contract=off) over the work lists of BOTH graphs in one grid.  The transpose is two sequences on the CSC
+//    dinv = 0 for an empty row.  The row-class walk of row_walk.h (small rows by lane group, medium rows by wave, hubs as
+//    128-edge tasks + a finalize; rows gathered unscaled and multiplied by dinv[src]; fixed order, no floating-point
+//    atomics; -ffp-contract=off) over the work lists of BOTH graphs in one grid.  The transpose is two sequences on the CSC
 //    sides, the second adding into what the first stored.
 #include <algorithm>
 
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
@@ -201,16 +201,13 @@ static __global__ void k_h2gcn_dinv(const int32_t *__restrict__ rowptr, int64_t 
 
 // ---- the hop ----------------------------------------------------------------------------------------------------------
 // one adjacency's share of a launch
-struct H2Side {
+struct H2Side : RowSide {
     const float *src;            // column 0 of the gathered slice
     float *dst;                  // column 0 of the W columns this side stores
     int64_t ld_src, ld_dst;
     const float *dinv;           // [N]
     float *partial;              // [n_tasks, W]
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB, nb;            // workgroups: split tasks, wave rows, all
+    int nb;                      // workgroups of this side (split tasks, wave rows and small rows)
     int col0;                    // this side's first column in the epilogue vectors
     int add;                     // dst += z instead of dst = z (the transpose's second sequence)
 };
@@ -220,33 +217,6 @@ struct H2Args {
     int sides, W, N;
     const float *rm, *invstd, *gamma, *beta;
 };
-
-template <int VEC, int G, int R>
-__device__ __forceinline__ void h2_gather(const H2Side &a, int W, int qs, int e0, int e1, int stride, int first, int lg,
-                                          Row<VEC, G, R> &acc)
-{
-    using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        float w[U];
-        bool act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] : 0;
-            w[u] = a.dinv[row];
-            x[u].load(a.src + (size_t)row * a.ld_src, W, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) {
-                x[u].scale(w[u]);
-                acc.add(x[u]);
-            }
-    }
-}
 
 // one stored element of column c (of this side's W) from z = dinv_r S: the norm, or the sum with what is there
 __device__ __forceinline__ float h2_element(const H2Args &a, const H2Side &s, int c, float z, const float *d)
@@ -278,51 +248,27 @@ __device__ __forceinline__ void h2_finish(const H2Args &a, const H2Side &s, int 
     }
 }
 
+// the workgroups of side 0, then those of side 1: S_i = sum dinv[src] * src[src, 0 .. W) (gather_rows), then h2_finish
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_h2gcn_hop(const H2Args a)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
     int b = blockIdx.x;
     const bool second = b >= a.s[0].nb;
     if (second) b -= a.s[0].nb;
-    const H2Side &s = second ? a.s[1] : a.s[0];
+    const H2Side s = second ? a.s[1] : a.s[0];
     RowT acc;
-    acc.zero();
-    if (b < s.nbA + s.nbB) {
-        const bool task = b < s.nbA;
-        const int tq = b * WAVES + wave;
-        const int slot = s.n_split + (b - s.nbA) * WAVES + wave;
-        const bool live = task ? tq < s.n_tasks : slot < s.n_med_end;          // (wave-uniform)
-        if (live) {
-            const int seg = s.perm[task ? s.task_slot[tq] : slot];
-            const int e0 = task ? s.task_chunk[tq] * CHUNK : 0;
-            const int qs = s.ptr[seg];
-            const int deg = s.ptr[seg + 1] - qs;
-            const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            h2_gather<VEC, G, R>(s, a.W, qs, e0, e1, NG, gid, lg, acc);
-            acc.reduce_across_groups();
-            if (gid == 0) {
-                if (task) acc.store(s.partial + (size_t)tq * a.W, a.W, lg);
-                else h2_finish<VEC, G, R>(a, s, seg, lg, acc);
-            }
-        }
-    } else {
-        const int slot = s.n_med_end + ((b - s.nbA - s.nbB) * WAVES + wave) * NG + gid;
-        if (slot < a.N) {
-            const int seg = s.perm[slot];
-            const int qs = s.ptr[seg];
-            const int deg = s.ptr[seg + 1] - qs;
-            h2_gather<VEC, G, R>(s, a.W, qs, 0, deg, 1, 0, lg, acc);
-            h2_finish<VEC, G, R>(a, s, seg, lg, acc);
-        }
-    }
+    walk_rows<G>(
+        s, b, a.N, acc,
+        [&](int, int qs, int e0, int e1, int stride, int first, int lg, RowT &x) {
+            gather_rows<VEC, G, R, gather_unroll(R)>(s.src, s.ld_src, a.W, s.idx, qs, e0, e1, stride, first, lg, x,
+                                                     RowWeight{s.dinv});
+        },
+        [&](int tq, int lg, RowT &x) { x.store(s.partial + (size_t)tq * a.W, a.W, lg); },
+        [&](int seg, int, int lg, RowT &x) { h2_finish<VEC, G, R>(a, s, seg, lg, x); });
 }
 
-// split segments of either side: the sum of the tasks' partial rows in k_gcn_hop_fin's order, then h2_finish's
-// arithmetic per element
+// split segments of either side: the sum of the tasks' partial rows, then h2_finish's arithmetic per element
 static __global__ __launch_bounds__(256) void k_h2gcn_hop_fin(const H2Args a)
 {
     __shared__ float sm[4][64];
@@ -337,37 +283,19 @@ static __global__ __launch_bounds__(256) void k_h2gcn_hop_fin(const H2Args a)
     float *d = s.dst + (size_t)r * s.ld_dst;
     for (int c0 = 0; c0 < a.W; c0 += 64) {
         const int c = c0 + cl;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        if (c < a.W) {
-            int t = t0 + q;
-            for (; t + 12 < t1; t += 16) {
-                v0 += s.partial[(size_t)t * a.W + c];
-                v1 += s.partial[(size_t)(t + 4) * a.W + c];
-                v2 += s.partial[(size_t)(t + 8) * a.W + c];
-                v3 += s.partial[(size_t)(t + 12) * a.W + c];
-            }
-            for (; t < t1; t += 4) v0 += s.partial[(size_t)t * a.W + c];
-        }
-        sm[q][cl] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
-        if (q == 0 && c < a.W) {
-            const float z = ((sm[0][cl] + sm[1][cl]) + (sm[2][cl] + sm[3][cl])) * di;
-            d[c] = h2_element(a, s, c, z, d);
-        }
+        const float sum = combine_task_sums(sm, sum_task_partials(s.partial, a.W, t0, t1, c, q), q, cl);
+        if (q == 0 && c < a.W) d[c] = h2_element(a, s, c, sum * di, d);
         __syncthreads();
     }
 }
 
 template <int VEC, int G, int R> int launch_h2gcn_hop(const H2Args &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     H2Args a = a0;
     int blocks = 0, fin = 0;
     for (int i = 0; i < a.sides; ++i) {
         H2Side &s = a.s[i];
-        s.nbA = ceil_div(s.n_tasks, WAVES);
-        s.nbB = ceil_div(s.n_med_end - s.n_split, WAVES);
-        s.nb = s.nbA + s.nbB + ceil_div(a.N - s.n_med_end, (int64_t)WAVES * NG);
+        s.nb = plan_side(s, a.N, 64 / G);
         blocks += s.nb;
         fin += s.n_split;
     }
@@ -377,38 +305,11 @@ template <int VEC, int G, int R> int launch_h2gcn_hop(const H2Args &a0, hipStrea
     return SNGNN_OK;
 }
 
-// (G, R) of the layouts a hop can take: row_cfg(W)'s, and its groups with 2 or 4 times the steps (a narrower vector)
-template <int VEC> static int dispatch_h2gcn_hop_gr(int g, int r, const H2Args &a, hipStream_t st)
-{
-#define H2_CASE(G_, R_) case G_ * 100 + R_: return launch_h2gcn_hop<VEC, G_, R_>(a, st);
-    switch (g * 100 + r) {
-        H2_CASE(8, 1) H2_CASE(16, 1) H2_CASE(32, 1) H2_CASE(64, 1) H2_CASE(64, 2) H2_CASE(64, 4) H2_CASE(64, 8)
-    default: break;
-    }
-    if constexpr (VEC < 4) {
-        switch (g * 100 + r) {
-            H2_CASE(8, 2) H2_CASE(16, 2) H2_CASE(32, 2)
-        default: break;
-        }
-    }
-    if constexpr (VEC == 1) {
-        switch (g * 100 + r) {
-            H2_CASE(8, 4) H2_CASE(16, 4) H2_CASE(32, 4)
-        default: break;
-        }
-    }
-#undef H2_CASE
-    set_error("unsupported channel layout");
-    return SNGNN_EINVAL;
-}
-
 static int run_h2gcn_hop(int vec, int g, int r, const H2Args &a, hipStream_t st)
 {
-    switch (vec) {
-    case 4: return dispatch_h2gcn_hop_gr<4>(g, r, a, st);
-    case 2: return dispatch_h2gcn_hop_gr<2>(g, r, a, st);
-    default: return dispatch_h2gcn_hop_gr<1>(g, r, a, st);
-    }
+    return dispatch_slice_layout(vec, g, r, [&](auto v, auto g_, auto r_) {
+        return launch_h2gcn_hop<decltype(v)::value, decltype(g_)::value, decltype(r_)::value>(a, st);
+    });
 }
 
 // H2GCN's A1 and A2: unpartitioned, no loop added, every loop removed
@@ -495,7 +396,7 @@ extern "C" int64_t sngnn_h2gcn_workspace_bytes(const sngnn_graph_t *g, int W)
 {
     RowCfg cfg;
     if (g == nullptr || !row_cfg(W, cfg)) return 0;
-    return up256((int64_t)std::max(g->n_tasks, g->n_stasks) * W * 4) + 256;
+    return task_partial_bytes(g, W) + 256;
 }
 
 extern "C" int sngnn_h2gcn_hop(const sngnn_graph_t *g1, const sngnn_graph_t *g2, const sngnn_h2gcn_hop_t *h,

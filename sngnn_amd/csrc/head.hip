@@ -11,16 +11,11 @@
 //                    chunks accumulate in registers and a second kernel adds the partials
 //                    in fixed order (deterministic, no float atomics).
 // Both are HBM-bound streams: 4 N C (+ 4 N C for the gradient) and 4 N (F + C) bytes.
+#include "device_utils.h"
 #include "head_row.h"
 
 namespace sngnn {
 
-__device__ __forceinline__ float wsum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 __device__ __forceinline__ float wmax(float v)
 {
 #pragma unroll
@@ -121,9 +116,9 @@ __global__ __launch_bounds__(256) void k_head_rows(const float *__restrict__ z, 
             }
         }
     }
-    loss = wsum(loss);
-    corr = wsum(corr);
-    if constexpr (TWO) { lossb = wsum(lossb); corrb = wsum(corrb); }
+    loss = wave_sum_f(loss);
+    corr = wave_sum_f(corr);
+    if constexpr (TWO) { lossb = wave_sum_f(lossb); corrb = wave_sum_f(corrb); }
     if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; s_lossb[wave] = lossb; s_corrb[wave] = corrb; }
     __syncthreads();
     if (threadIdx.x == 0 && TWO) {
@@ -211,9 +206,9 @@ __global__ __launch_bounds__(256) void k_head_groups(const float *__restrict__ z
             if (gi && in) *reinterpret_cast<float4 *>(gi) = head_row_grad(hr, scale);
         }
     }
-    loss = wsum(loss);
-    corr = wsum(corr);
-    if constexpr (TWO) { lossb = wsum(lossb); corrb = wsum(corrb); }
+    loss = wave_sum_f(loss);
+    corr = wave_sum_f(corr);
+    if constexpr (TWO) { lossb = wave_sum_f(lossb); corrb = wave_sum_f(corrb); }
     if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; s_lossb[wave] = lossb; s_corrb[wave] = corrb; }
     __syncthreads();
     if (threadIdx.x == 0 && TWO) {
@@ -262,7 +257,7 @@ __global__ __launch_bounds__(256) void k_head(const float *__restrict__ z, const
             }
             const float mx = wmax(v[r]);
             const float e = lane < C ? expf(v[r] - mx) : 0.f;
-            const float se = wsum(e);
+            const float se = wave_sum_f(e);
             const int arg = wmin_i((lane < C && v[r] == mx) ? lane : C);
             const float zy = __shfl(v[r], yi[r], 64);
             loss += -(zy - mx - logf(se));
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(256) void k_head(const float *__restrict__ z, const
                 se += expf(t - mx);
                 if (t == mx) arg = min(arg, c);
             }
-            se = wsum(se);
+            se = wave_sum_f(se);
             arg = wmin_i(arg);                      // first maximum, like torch.max on the CPU
             const int yy = (int)y[i];
             loss += -(zi[yy] - mx - logf(se));

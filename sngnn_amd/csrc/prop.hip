@@ -2,8 +2,8 @@
 // models/models.py:1191-1208 and PyG's APPNP as models.py:1033 uses it.
 //     A^ = D^-1/2 (A + I) D^-1/2,  deg_i = in-degree with the loop,  dinv = deg^-1/2
 //     (A^ x)_i = sum_{e -> i} dinv_src dinv_i x_src = dinv_i * sum_{e -> i} u_src     with u = dinv . x
-// The kernels carry the SCALED iterate u, so a hop is an unweighted row gather-sum (the skeleton of
-// adj_linear_impl.h: small rows by lane group, medium rows by wave, hubs as 128-edge tasks + a finalize; fixed
+// The kernels carry the SCALED iterate u, so a hop is an unweighted row gather-sum (the row-class walk of
+// row_walk.h: small rows by lane group, medium rows by wave, hubs as 128-edge tasks + a finalize; fixed
 // summation order, no atomics) with a store epilogue that does the rest of the recurrence:
 //     z_i = a x0_i + b (dinv_i S_i),   [acc_i += c z_i,]   [dot += <z_i, xd_i>,]   store dinv_i z_i | z_i (last hop)
 // a, b, c are read from device memory (they are functions of a parameter).  Every product and sum is rounded
@@ -13,14 +13,14 @@
 //                  grad_gamma_k = <t_k, x>: per-workgroup partial dots in double from the hops' own launches,
 //                  one reducer launch adds them in a fixed order                             (CSC side)
 //   APPNP          x_{k+1} = alpha h + (1 - alpha) A^ x_k; its backward is the same recurrence on A^T
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
 constexpr int PROP_INIT_BLOCKS = 1024;
 
-struct PropArgs {
+struct PropArgs : RowSide {
     const float *u;             // scaled iterate to gather  [N, C]
     const float *x0;            // [N, C] or nullptr: the a x0 term
     const float *dinv;          // [N]
@@ -32,33 +32,7 @@ struct PropArgs {
     int scaled;                 // store dinv_i z_i (the next iterate) instead of z_i
     float *partial;             // [n_tasks, C]
     int C, N;
-    const int32_t *ptr, *idx, *perm;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
 };
-
-template <int VEC, int G, int R>
-__device__ __forceinline__ void prop_gather(const PropArgs &a, int qs, int e0, int e1, int stride, int first, int lg,
-                                            Row<VEC, G, R> &acc)
-{
-    using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
-    for (int base = e0 + first; base < e1; base += stride * U) {
-        RowT x[U];
-        bool act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = base + u * stride;
-            act[u] = t < e1;
-            const int row = act[u] ? a.idx[qs + t] : 0;
-            x[u].load(a.u + (size_t)row * a.C, a.C, lg);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (act[u]) acc.add(x[u]);
-    }
-}
 
 // the epilogue of row r from its gathered sum s; returns this lane's share of <z_r, xd_r>
 template <int VEC, int G, int R>
@@ -98,64 +72,32 @@ __device__ __forceinline__ double prop_finish(const PropArgs &a, int r, int lg, 
     return d;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
+// S_i = sum u[src] (gather_rows), then prop_finish; the finishing lanes' shares of the dot are added per workgroup
 template <int VEC, int G, int R>
 __global__ __launch_bounds__(BLOCK) void k_prop(const PropArgs a)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int NG = 64 / G;
     __shared__ double sd[WAVES];
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int gid = lane / G, lg = lane % G;
     const int b = blockIdx.x;
     RowT acc;
-    acc.zero();
     double d = 0.0;
-    if (b < a.nbA + a.nbB) {
-        // split task or one wave per segment
-        const bool task = b < a.nbA;
-        const int tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        const bool live = task ? tq < a.n_tasks : slot < a.n_med_end;          // (wave-uniform)
-        if (live) {
-            const int seg = a.perm[task ? a.task_slot[tq] : slot];
-            const int e0 = task ? a.task_chunk[tq] * CHUNK : 0;
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            const int e1 = task ? min(deg, e0 + CHUNK) : deg;
-            prop_gather<VEC, G, R>(a, qs, e0, e1, NG, gid, lg, acc);
-            acc.reduce_across_groups();
-            if (gid == 0) {
-                if (task) acc.store(a.partial + (size_t)tq * a.C, a.C, lg);
-                else d = prop_finish<VEC, G, R>(a, seg, lg, acc);
-            }
-        }
-    } else {
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        if (slot < a.N) {
-            const int seg = a.perm[slot];
-            const int qs = a.ptr[seg];
-            const int deg = a.ptr[seg + 1] - qs;
-            prop_gather<VEC, G, R>(a, qs, 0, deg, 1, 0, lg, acc);
-            d = prop_finish<VEC, G, R>(a, seg, lg, acc);
-        }
-    }
+    walk_rows<G>(
+        a, b, a.N, acc,
+        [&](int, int qs, int e0, int e1, int stride, int first, int lg, RowT &s) {
+            gather_rows<VEC, G, R, gather_unroll(R)>(a.u, a.C, a.C, a.idx, qs, e0, e1, stride, first, lg, s, NoWeight{});
+        },
+        [&](int tq, int lg, RowT &s) { s.store(a.partial + (size_t)tq * a.C, a.C, lg); },
+        [&](int seg, int, int lg, RowT &s) { d = prop_finish<VEC, G, R>(a, seg, lg, s); });
     if (a.xd && b >= a.nbA) {                          // (block-uniform) the workgroup's partial dot, fixed order
         d = wave_sum_d(d);
-        if (lane == 0) sd[wave] = d;
+        if (lane_id() == 0) sd[threadIdx.x >> 6] = d;
         __syncthreads();
         if (threadIdx.x == 0) a.dotpart[b - a.nbA] = (sd[0] + sd[1]) + (sd[2] + sd[3]);
     }
 }
 
-// split segments: the sum of the tasks' partial rows in k_adj_fin's order, then the epilogue per element (the
-// arithmetic of prop_finish); the row's dot is partial number part0 + p
+// split segments: the sum of the tasks' partial rows, then the epilogue per element (the arithmetic of prop_finish);
+// the row's dot is partial number part0 + p
 static __global__ __launch_bounds__(256) void k_prop_fin(const PropArgs a, int part0)
 {
     __shared__ float s[4][64];
@@ -167,22 +109,10 @@ static __global__ __launch_bounds__(256) void k_prop_fin(const PropArgs a, int p
     double d = 0.0;
     for (int c0 = 0; c0 < a.C; c0 += 64) {
         const int c = c0 + cl;
-        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
-        if (c < a.C) {
-            int t = t0 + q;
-            for (; t + 12 < t1; t += 16) {
-                v0 += a.partial[(size_t)t * a.C + c];
-                v1 += a.partial[(size_t)(t + 4) * a.C + c];
-                v2 += a.partial[(size_t)(t + 8) * a.C + c];
-                v3 += a.partial[(size_t)(t + 12) * a.C + c];
-            }
-            for (; t < t1; t += 4) v0 += a.partial[(size_t)t * a.C + c];
-        }
-        s[q][cl] = (v0 + v1) + (v2 + v3);
-        __syncthreads();
+        const float sum = combine_task_sums(s, sum_task_partials(a.partial, a.C, t0, t1, c, q), q, cl);
         if (q == 0 && c < a.C) {
             const size_t at = (size_t)r * a.C + c;
-            float z = (((s[0][cl] + s[1][cl]) + (s[2][cl] + s[3][cl]))) * di;
+            float z = sum * di;
             if (a.b) z = z * *a.b;
             if (a.x0) z = a.x0[at] * *a.a + z;
             if (a.acc) a.acc[at] = a.acc[at] + *a.c * z;
@@ -248,13 +178,10 @@ static __global__ void k_prop_dinv(const int32_t *__restrict__ rowptr, int64_t N
 
 template <int VEC, int G, int R> int launch_prop(const PropArgs &a0, hipStream_t st)
 {
-    constexpr int NG = 64 / G;
     PropArgs a = a0;
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * NG);
-    if (a.nbA + a.nbB + nbC > 0) k_prop<VEC, G, R><<<a.nbA + a.nbB + nbC, BLOCK, 0, st>>>(a);
-    if (a.n_split > 0) k_prop_fin<<<a.n_split, 256, 0, st>>>(a, a.nbB + nbC);
+    const int grid = plan_side(a, a.N, 64 / G);
+    if (grid > 0) k_prop<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
+    if (a.n_split > 0) k_prop_fin<<<a.n_split, 256, 0, st>>>(a, grid - a.nbA);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -277,8 +204,7 @@ static int prop_parts(const sngnn_graph_t *g, bool transpose, const RowCfg &cfg)
 {
     PropArgs a;
     prop_side(g, transpose, a);
-    return ceil_div(a.n_med_end - a.n_split, WAVES) + ceil_div(a.N - a.n_med_end, (int64_t)WAVES * (64 / cfg.g)) +
-           a.n_split;
+    return plan_side(a, a.N, 64 / cfg.g) - a.nbA + a.n_split;
 }
 
 struct PropLayout { int64_t u1, partial, dots, total, stride; };
@@ -289,7 +215,7 @@ static PropLayout prop_layout(const sngnn_graph_t *g, int C, int K, const RowCfg
     const int64_t rows = up256(g->N * (int64_t)C * 4);
     L.u1 = rows;
     L.partial = 2 * rows;
-    L.dots = L.partial + up256((int64_t)std::max(g->n_tasks, g->n_stasks) * C * 4);
+    L.dots = L.partial + task_partial_bytes(g, C);
     L.stride = std::max<int64_t>(PROP_INIT_BLOCKS, std::max(prop_parts(g, false, cfg), prop_parts(g, true, cfg)));
     L.total = L.dots + up256((int64_t)(K + 1) * L.stride * 8);
     return L;

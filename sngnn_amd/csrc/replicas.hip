@@ -27,13 +27,6 @@ namespace sngnn {
 
 namespace {
 
-__device__ __forceinline__ float rep_wsum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------
 // Unpack + bias + F.normalize: union row u = r N + i <- hs[i, r C .. r C + C) + bias[r].  The
 // lane layout, loop and normalisation are k_normalize_rows' (agg_fwd_roles.h), so n / nrm / filt are
@@ -321,9 +314,9 @@ __global__ __launch_bounds__(256) void k_rep_head_rows(const float *__restrict__
             }
         }
     }
-    loss = rep_wsum(loss);
-    corr = rep_wsum(corr);
-    if constexpr (TWO) { lossb = rep_wsum(lossb); corrb = rep_wsum(corrb); }
+    loss = wave_sum_f(loss);
+    corr = wave_sum_f(corr);
+    if constexpr (TWO) { lossb = wave_sum_f(lossb); corrb = wave_sum_f(corrb); }
     if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; s_lossb[wave] = lossb; s_corrb[wave] = corrb; }
     __syncthreads();
     if (threadIdx.x == 0 && TWO) {
@@ -405,9 +398,9 @@ __global__ __launch_bounds__(256) void k_rep_head_groups(const float *__restrict
             if (gi && in) *reinterpret_cast<float4 *>(gi) = head_row_grad(hr, scale);
         }
     }
-    loss = rep_wsum(loss);
-    corr = rep_wsum(corr);
-    if constexpr (TWO) { lossb = rep_wsum(lossb); corrb = rep_wsum(corrb); }
+    loss = wave_sum_f(loss);
+    corr = wave_sum_f(corr);
+    if constexpr (TWO) { lossb = wave_sum_f(lossb); corrb = wave_sum_f(corrb); }
     if (lane == 0) { s_loss[wave] = loss; s_corr[wave] = corr; s_lossb[wave] = lossb; s_corrb[wave] = corrb; }
     __syncthreads();
     if (threadIdx.x == 0 && TWO) {

@@ -20,20 +20,6 @@ namespace sngnn {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ float wave_sum_f(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // inv[i] = 1 / max(||x_i||, eps)   (one wave per row; F.normalize semantics)
 __global__ __launch_bounds__(256) void k_row_inv_norm(const float *__restrict__ x, int64_t N,
                                                       int64_t F, float *__restrict__ inv,

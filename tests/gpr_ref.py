@@ -229,6 +229,34 @@ def degree_graph(seed=0):
     return ei[:, torch.randperm(ei.size(1), generator=gen)].contiguous(), n
 
 
+HUB_DEGREE = 2200      # 18 tasks of 128 entries: the finalize's four-chain loop (t + 12 < t1) first runs at 13 tasks
+
+
+def hub_graph(seed=3):
+    """One directed graph of 2 400 nodes with a hub on either side: node 0 has HUB_DEGREE in-edges, node 1 HUB_DEGREE
+    out-edges (distinct partners drawn from the pool 2 .. 2398; neither hub has another edge), over 7 000 background
+    edges among the pool with 60 duplicates and 4 original self loops; node 2399 is isolated.  Returns (edge_index, n)
+    as drawn: a family builds its own graph of it (loops replaced, kept raw, or made unique and loop-free)."""
+    gen = torch.Generator().manual_seed(seed)
+    n, lo, hi = 2400, 2, 2399
+    pool = torch.arange(lo, hi)
+    src = pool[torch.randperm(pool.numel(), generator=gen)[:HUB_DEGREE]]
+    tgt = pool[torch.randperm(pool.numel(), generator=gen)[:HUB_DEGREE]]
+    bg = torch.randint(lo, hi, (2, 7000), generator=gen)
+    loops = torch.tensor([[20, 21, 22, 23], [20, 21, 22, 23]])
+    ei = torch.cat([torch.stack([src, torch.zeros_like(src)]), torch.stack([torch.ones_like(tgt), tgt]), bg, bg[:, :60],
+                    loops], dim=1)
+    return ei[:, torch.randperm(ei.size(1), generator=gen)].contiguous(), n
+
+
+def split_tasks(edge_index, num_nodes, chunk=128):
+    """(most tasks of a target, most tasks of a source) when every node's in- / out-entries are dealt out in
+    ``chunk``-entry tasks: the entries counted as ``edge_index`` lists them."""
+    ei = edge_index.cpu().to(torch.int64)
+    ind, outd = torch.bincount(ei[1], minlength=num_nodes), torch.bincount(ei[0], minlength=num_nodes)
+    return int(-(-ind.max() // chunk)), int(-(-outd.max() // chunk))
+
+
 def degrees(edge_index, num_nodes):
     """(in-degree, out-degree) with the loop, int64 [N] each."""
     ei, _, _ = gcn_norm(edge_index, num_nodes, torch.float64)

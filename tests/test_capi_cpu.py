@@ -102,7 +102,7 @@ def test_hot_path_sources_hold_no_host_synchronisation():
     ``sngnn_profile_last_forward`` (bench.py's roofline leg, never on a model's path).  Graph construction
     (graph.hip), the toolbox statistics and the kNN builder are setup / analysis calls and may block."""
     hot = ("agg_fwd.hip", "agg_fwd_impl.h", "agg_fwd_filter.h", "agg_bwd.hip", "agg_bwd_impl.h", "attn.hip",
-           "attn_impl.h", "signed.hip", "signed_impl.h", "adj_linear.hip", "adj_linear_impl.h", "blend.hip",
+           "attn_impl.h", "signed.hip", "signed_impl.h", "adj_linear.hip", "adj_linear_impl.h", "row_walk.h", "blend.hip",
            "linear.hip", "head.hip", "head_row.h", "device_utils.h", "entry.h", "ws_layout.h", "fwd_plan.h",
            "agg_fwd_args.h", "agg_fwd_head.h", "agg_fwd_select.h", "agg_fwd_roles.h", "agg_fwd_fin.h")
     blocking = re.compile(r"\bhip(StreamSynchronize|DeviceSynchronize|EventSynchronize|Memcpy|MemcpyDtoH|Malloc|Free|"
