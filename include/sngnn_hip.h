@@ -20,6 +20,10 @@
  *   - ``stream`` is a hipStream_t passed as void* (NULL = the null stream);
  *     forward/backward entry points only enqueue work: no allocation, no host
  *     synchronisation, safe to capture in a hipGraph;
+ *   - every ``workspace`` (and ``head_workspace``) is dev scratch of the bytes the entry's ``*_workspace_bytes``
+ *     function returns for the same arguments: the call reads and writes only inside those bytes, its contents on
+ *     entry are unspecified (no result depends on them) and on return they mean nothing to the caller; one buffer
+ *     must not be shared by calls that may run concurrently (two streams);
  *   - every function returns 0 on success or a negative SNGNN_E* code;
  *     sngnn_last_error() gives the message of the calling thread's last failure.
  */
@@ -742,7 +746,7 @@ int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out, const floa
  * The graph: the edge list sorted STABLY by relation, built with add_loops = 0, remove_loops = 0 (every edge kept,
  * duplicates count once each), unpartitioned (SNGNN_EINVAL otherwise).  Its CSR rows are then grouped by relation:
  *   rel_ptr  dev i32 [N, R + 1]   offsets inside the row: entries [rel_ptr[i,r], rel_ptr[i,r+1]) of row i carry relation r
- *   rel_csc  dev i32 [E]          the relation of every CSC entry (the backward's scatter pass)
+ *   rel_csc  dev i32 [E]          the relation of every CSC entry (the backward's scatter pass; may be NULL when E == 0)
  *   w_csr    dev f32 [E]          the edge weights in CSR order, or NULL (= 1); data, no gradient
  * Limits: 1 <= R <= 16, C >= 1, R * C <= SNGNN_MAX_CHANNELS (SNGNN_ERANGE otherwise, nothing launched).
  * P, self_rows, grad_P and grad_self are row-strided (strides in floats, multiples of the row vector width 4 | 2 | 1

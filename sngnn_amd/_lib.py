@@ -265,13 +265,14 @@ def call(name, device, *args):
         check(rc, name)
 
 
-_ws_cache = {}
+_ws_cache = {}          # (purpose, device, stream) -> every buffer handed out for it, the live one last
 
 
 def workspace(key, nbytes, device):
-    """Grow-only scratch per (purpose, device) for the entries whose ``*_workspace_bytes`` depends on the call."""
-    ws = _ws_cache.get((key, str(device)))
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-        _ws_cache[(key, str(device))] = ws
-    return ws
+    """Grow-only scratch per (purpose, device, stream) for the entries whose ``*_workspace_bytes`` depends on the call.
+    Lifetime rule: a buffer handed out once is never released while the process lives - a captured epoch launches on
+    its address.  One that is outgrown stays in its slot's list, behind a new one of at least twice its size."""
+    held = _ws_cache.setdefault((key, str(device), stream(device) if torch.device(device).type == "cuda" else None), [])
+    if not held or held[-1].numel() < nbytes:
+        held.append(torch.empty(max(int(nbytes), 256, 2 * held[-1].numel() if held else 0), dtype=torch.uint8, device=device))
+    return held[-1]

@@ -636,8 +636,9 @@ extern "C" int sngnn_wrgat_backward(const sngnn_graph_t *g, const float *grad_ou
 {
     WR_CHECKS(g, R, C);
     if (g->N == 0) return SNGNN_OK;
-    SN_REQUIRE(grad_out && P && rel_ptr && rel_csc && atten && scores && ml && workspace && (out || !relu), SNGNN_EINVAL,
-               "NULL argument");
+    // (rel_csc has one element per edge: a graph without edges has none to point at, and pass S reads none)
+    SN_REQUIRE(grad_out && P && rel_ptr && (rel_csc || g->Ep == 0) && atten && scores && ml && workspace && (out || !relu),
+               SNGNN_EINVAL, "NULL argument");
     SN_REQUIRE(P_stride >= (int64_t)R * C && (!grad_P || grad_P_stride >= (int64_t)R * C) &&
                    (!grad_self || grad_self_stride >= C), SNGNN_EINVAL, "a row stride is too short");
     SN_REQUIRE(rows_aligned((uintptr_t)cfg.vec * 4, {grad_out, P, atten, grad_P, grad_self, workspace}) &&

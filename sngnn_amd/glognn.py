@@ -95,8 +95,8 @@ def gram(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
         b = check_rows(b, a.size(0), "b", max_channels=MAX_WIDTH)
         if b.shape != a.shape or b.device != a.device:
             raise ValueError(f"b must have a's shape {tuple(a.shape)} and device")
-    # (one buffer per device AND stream, as Graph.scratch keeps them: calls from two streams never share partials)
-    ws = _lib.workspace(("glognn_gram", _lib.stream(a.device)), _lib.load().sngnn_glognn_gram_workspace_bytes(a.size(1)), a.device)
+    # (one buffer per device AND stream - _lib.workspace's key, as Graph.scratch's: calls from two streams never share partials)
+    ws = _lib.workspace("glognn_gram", _lib.load().sngnn_glognn_gram_workspace_bytes(a.size(1)), a.device)
     return _gram(a, b, ws)[0]
 
 

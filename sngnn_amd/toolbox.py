@@ -117,8 +117,7 @@ def _hist_scan(x, y32, edges, bins):
     groups = 1 if y32 is None else 2
     counts = torch.empty((groups, bins + 2), dtype=torch.int64, device=x.device)
     stats = torch.empty(3, dtype=torch.float64, device=x.device)
-    ws = torch.empty(max(int(lib.sngnn_cosine_hist_workspace_bytes(n, f, bins, groups)), 256), dtype=torch.uint8,
-                     device=x.device)
+    ws = _lib.workspace("cosine_hist", lib.sngnn_cosine_hist_workspace_bytes(n, f, bins, groups), x.device)
     _lib.call("sngnn_cosine_hist", x.device, x, n, f, y32, edges, bins, counts, stats, ws)
     return counts, stats
 
@@ -397,7 +396,7 @@ def knn_graph(x: torch.Tensor, k: int, exclude_self: bool = True):
     lib = _lib.load()
     idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
     sim = torch.empty((n, k), dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(lib.sngnn_knn_workspace_bytes(n, int(k))), 256), dtype=torch.uint8, device=x.device)
+    ws = _lib.workspace("knn", lib.sngnn_knn_workspace_bytes(n, int(k)), x.device)
     _lib.call("sngnn_knn_graph", x.device, x, n, f, int(k), int(bool(exclude_self)), idx, sim, ws)
     return idx.long(), sim
 

@@ -281,3 +281,27 @@ def test_the_library_refuses_what_is_outside_its_limits(cuda):
         with pytest.raises(ValueError, match=r"\(-1\)"):
             _lib.call("sngnn_wrgat_forward", cuda, g.handle, t, 64, None, 0, None, i32, None, t, 2, 4, 0.2, 0, out, t, t, t)
     assert bool((out == 7.0).all()), "a refused call launches nothing"
+
+
+def test_a_graph_without_edges_trains(cuda, monkeypatch):
+    """No edge at all: ``rel_csc`` and ``w_csr`` have no element to point at (they go in as NULL) and the layer is its
+    root term - ``relu(self_rows + bias)`` exactly, forward and backward (``sngnn_wrgat_backward`` used to refuse the
+    NULL ``rel_csc`` with SNGNN_EINVAL)."""
+    from sngnn_amd import ops, wrgat
+    monkeypatch.setattr(wrgat, "FUSE_WRGAT", True)
+    n, r, c = 50, 3, 5
+    gen = torch.Generator().manual_seed(3)
+    none = torch.empty((2, 0), dtype=torch.int64, device=cuda)
+    adj = ops.TypedAdjacency(none, none[0], torch.empty(0, device=cuda), n, r)
+    P, atten, self_rows, bias = (torch.randn(s, generator=gen).to(cuda).requires_grad_(True)
+                                 for s in ((n, r * c), (r, 2 * c), (n, c), (c,)))
+    g = torch.randn(n, c, generator=gen).to(cuda)
+    out = ops.wrgat_conv(P, atten, self_rows, bias, adj, relu=True)
+    assert type(out.grad_fn).__name__.startswith("_WRGATConv"), "the fused arm"
+    out.backward(g)
+    want = torch.relu(self_rows.detach() + bias.detach())
+    assert torch.equal(out.detach(), want)
+    gm = g * (want > 0)
+    assert torch.equal(self_rows.grad, gm)
+    assert torch.equal(P.grad, torch.zeros_like(P)) and torch.equal(atten.grad, torch.zeros_like(atten))
+    assert (bias.grad.double() - gm.double().sum(0)).abs().max() <= 2.0 ** -22 * gm.double().abs().sum(0).max()

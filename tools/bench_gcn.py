@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sngnn_amd import GCN, GCNConv, MixHop, MixHopLayer, _lib, gcn, models, ops, synth  # noqa: E402
+from sngnn_amd import GCN, GCNConv, MixHop, MixHopLayer, gcn, models, synth  # noqa: E402
 from sngnn_amd import train as T  # noqa: E402
 from sngnn_amd.graph import GLOBAL_CACHE, LOOPS_REPLACE  # noqa: E402
 
@@ -134,15 +134,6 @@ def main():
 
     def worst(a, b):
         return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-    # The scratch of sngnn_linear_wgrad and of the fused batch norm is ONE grow-only buffer per device: a wider layer
-    # replaces it, and a graph captured before that keeps the address of the buffer that was dropped (the next capture
-    # empties the allocator's cache, and its replay then faults).  This process captures layers of several widths one
-    # after the other, so both are sized for the widest first.
-    wide = (HOPS + 1) * C
-    shapes = [(C, F_IN), (wide, F_IN), (C, f), (classes, C), (wide, f), ((HOPS + 1) * classes, wide), (classes, (HOPS + 1) * classes)]
-    _lib.workspace("wgrad", max(int(_lib.load().sngnn_linear_wgrad_workspace_bytes(n, c, fin)) for c, fin in shapes), dev)
-    ops.bn_train_workspace(wide, dev)
 
     gen = torch.Generator().manual_seed(C)
     x = torch.randn(n, F_IN, generator=gen).to(dev)

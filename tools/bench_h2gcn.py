@@ -34,7 +34,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sngnn_amd import H2GCN, _lib, h2gcn, ops, synth  # noqa: E402
+from sngnn_amd import H2GCN, h2gcn, ops, synth  # noqa: E402
 from sngnn_amd import train as T  # noqa: E402
 from sngnn_amd.graph import Graph  # noqa: E402
 
@@ -198,9 +198,6 @@ def main():
                       train_mask=torch.from_numpy(np.asarray(z["train_mask0"]).astype(bool)).to(dev),
                       val_mask=torch.from_numpy(np.asarray(z["val_mask0"]).astype(bool)).to(dev),
                       test_mask=torch.from_numpy(np.asarray(z["test_mask0"]).astype(bool)).to(dev))
-    wide = HIDDEN * 7
-    _lib.workspace("wgrad", max(int(_lib.load().sngnn_linear_wgrad_workspace_bytes(n, c, fin))
-                                for c, fin in ((HIDDEN, F_IN), (classes, wide))), dev)
     epochs = {}
     for fz in (True, False):
         h2gcn.FUSE_H2GCN = fz
