@@ -1028,6 +1028,43 @@ int sngnn_glognn_backward(const sngnn_graph_t *g, const float *grad_out, const f
                           const double *gG2, const float *orders_weight, int orders, double beta, double gamma, int C,
                           float *grad_x, float *grad_h0, double *grad_w, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------------
+ * LINKX's join of the two embeddings (models/models.py:1098-1146): csrc/linkx.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * Replaces: models.py:1135-1143 - the log_softmax at the end of mlpA's and mlpX's MLP.forward (:476), torch.cat,
+ * self.W, the two adds and F.relu (inner_dropout and inner_activation off):
+ *     a = log_softmax(zA), x = log_softmax(zX)     (lsm == 0: a = zA, x = zX)
+ *     y = relu(a Wa^T + x Wx^T + b + a + x),       W = [Wa | Wx]
+ * for the last linears' outputs zA, zX of the two MLPs.  Row-local, no graph: the rows are streamed once in 32-row
+ * tiles (64 rows and 512 threads above H = 64) through LDS with W resident in LDS - both H x H halves for H <= 96, one after the other (two launches, the
+ * same bits) above; the row's maximum and sum (of fp32 exponentials, added and logged in double) are taken in the tile
+ * before the product; a dot product is four
+ * interleaved fp32 fma chains added pairwise; per element t = dotA + a, t + dotX, + b, + x, max(., 0), every product
+ * and sum rounded separately, fixed order, no atomics.
+ *   zA, zX  dev f32 [N, H]      W  dev f32 [H, 2H] row-major (W.weight)      b  dev f32 [H]
+ *   ax      dev f32 [N, 2H]     [a | x]: the one tensor the backward saves - sngnn_linear_wgrad(g, ax) with F = 2H
+ *                               is the weight gradient
+ *   y       dev f32 [N, H]
+ * 1 <= H <= SNGNN_LINKX_MAX_H (sngnn_linkx_join_supported; SNGNN_ERANGE otherwise), any N >= 0; ax and y must not
+ * alias the inputs (SNGNN_EINVAL).  Only enqueues.
+ */
+#define SNGNN_LINKX_MAX_H 128
+int sngnn_linkx_join_supported(int H);
+int sngnn_linkx_join_forward(const float *zA, const float *zX, const float *W, const float *b, int64_t N, int H, int lsm,
+                             float *ax, float *y, void *stream);
+/*
+ * Replaces: autograd of the same lines w.r.t. the two embeddings, in one pass with the same tiling:
+ *     g = grad_y [y > 0]                            (stored: the weight and bias gradients read it)
+ *     tA = g + g Wa,  tX = g + g Wx
+ *     grad_zA = tA - exp(a) sum_j tA_j              (lsm == 0: grad_zA = tA), the same for X, a and x read from ax
+ *   grad_y, y  dev f32 [N, H]     ax  dev f32 [N, 2H]     W  dev f32 [H, 2H]
+ *   g, grad_zA, grad_zX  dev f32 [N, H], distinct from the inputs and from each other (SNGNN_EINVAL)
+ * Only enqueues.
+ */
+int sngnn_linkx_join_backward(const float *grad_y, const float *y, const float *ax, const float *W, int64_t N, int H,
+                              int lsm, float *g, float *grad_zA, float *grad_zX, void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -11,6 +11,7 @@ from .gcnnet import GCN, GCNJK, GCNConv, MixHop, MixHopLayer
 from .ggcn import GGCN, GGCNlayer_SP
 from .h2gcnnet import H2GCN, H2GCNConv
 from .gpr import APPNP, APPNP_Net, GPR_prop, GPRGNN, MLP
+from .linkxnet import LINK, LINK_Concat, LINKX
 from .mlpnorm import MLPNORM
 from .models import AGNN, SNGNN, SNGNN_Plus, SNGNN_Plus_Plus
 from .synth import Data
@@ -20,4 +21,4 @@ __all__ = ["SNConv", "SNConv_plus", "SNConv_plus_plus", "SNGNN", "SNGNN_Plus",
            "SNGNN_Plus_Plus", "AGNNConv", "AGNN", "GGCNlayer_SP", "GGCN", "MLP", "GPR_prop",
            "GPRGNN", "APPNP", "APPNP_Net", "GATConv", "GAT", "GraphConvolution2", "ACMGCN", "GCN2Conv",
            "GCNII", "GCNConv", "GCN", "GCNJK", "MixHopLayer", "MixHop", "H2GCNConv",
-           "H2GCN", "WeightedRGATConv", "WRGAT", "MLPNORM", "Data"]
+           "H2GCN", "WeightedRGATConv", "WRGAT", "MLPNORM", "LINK", "LINK_Concat", "LINKX", "Data"]

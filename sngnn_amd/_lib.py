@@ -33,13 +33,10 @@ SIGNATURES = {
     "sngnn_graph_destroy": (None, [_vp]),
     "sngnn_graph_num_nodes": (_i64, [_vp]), "sngnn_graph_num_total_nodes": (_i64, [_vp]),
     "sngnn_graph_row_offset": (_i64, [_vp]), "sngnn_graph_num_edges": (_i64, [_vp]),
-    "sngnn_graph_max_in_degree": (_i64, [_vp]),
-    "sngnn_graph_src_min": (_i64, [_vp]),
-    "sngnn_graph_num_fused_nodes": (_i64, [_vp]),
-    "sngnn_graph_workspace_bytes": (_i64, [_vp, _i32]),
+    "sngnn_graph_max_in_degree": (_i64, [_vp]), "sngnn_graph_src_min": (_i64, [_vp]),
+    "sngnn_graph_num_fused_nodes": (_i64, [_vp]), "sngnn_graph_workspace_bytes": (_i64, [_vp, _i32]),
     "sngnn_graph_copy_array": (_i32, [_vp, _i32, _vp]),
-    "sngnn_graph_array_dev": (_vp, [_vp, _i32]),
-    "sngnn_graph_array_len": (_i64, [_vp, _i32]),
+    "sngnn_graph_array_dev": (_vp, [_vp, _i32]), "sngnn_graph_array_len": (_i64, [_vp, _i32]),
     "sngnn_agg_forward": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_normalize_rows": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
     "sngnn_filter_row_bytes": (_i64, [_i32]),
@@ -117,10 +114,11 @@ SIGNATURES = {
     "sngnn_glognn_solve_backward": (_i32, [_vp, _vp, _f64, _f64] + [_vp] * 4 + [_f64] * 3 + [_i32] + [_vp] * 4),
     "sngnn_glognn_workspace_bytes": (_i64, [_vp, _i32, _i32]), "sngnn_glognn_forward": (_i32, [_vp] * 5 + [_i32, _f64, _f64, _i32] + [_vp] * 4),
     "sngnn_glognn_backward": (_i32, [_vp] * 6 + [_i32, _f64, _f64, _i32] + [_vp] * 5),
+    "sngnn_linkx_join_supported": (_i32, [_i32]), "sngnn_linkx_join_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "sngnn_linkx_join_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
-    "sngnn_gather_floor_workspace_bytes": (_i64, []),
-    "sngnn_gather_floor": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "sngnn_gather_floor_workspace_bytes": (_i64, []), "sngnn_gather_floor": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_adj_linear_forward": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_adj_linear_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_head_workspace_bytes": (_i64, [_i64]),

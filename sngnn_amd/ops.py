@@ -22,6 +22,7 @@ from .gcn2 import gcn2_conv, gcn2_conv_plain, gcn2_map  # noqa: F401  (csrc/gcn2
 from .glognn import adj_matmul, glognn_norm, glognn_norm_plain, glognn_solve, glognn_solve_backward, gram  # noqa: F401  (csrc/glognn.hip)
 from .graph import Graph
 from .h2gcn import H2Adjacency, h2gcn_conv, h2gcn_conv_plain, two_hop_edge_index  # noqa: F401  (csrc/h2gcn.hip)
+from .linkx import linkx_join, linkx_join_plain  # noqa: F401  (csrc/linkx.hip)
 from .prop import _WeightedPropagate, appnp_propagate, gpr_propagate, weighted_propagate  # noqa: F401  (csrc/prop.hip)
 from .wrgat import TypedAdjacency, wrgat_conv, wrgat_conv_table  # noqa: F401  (csrc/wrgat.hip)
 
