@@ -37,12 +37,14 @@ int launch_wgrad_mfma(const float *g, const float *x, int64_t N, int C, int F, f
 
 // gat.hip, shared with wrgat.hip: the two score tables [N, H] from one read of xp [N, H, C] (rows ld floats apart, rows of
 // att_* lda apart; each score's C products summed in double), and the per-workgroup partials [blocks, 2, H * C] (f64) of
-// sum_n grad_a_src[n,h] xp[n,h,c] | sum_n grad_a_dst[n,h] xp[n,h,c], which a reducer adds in workgroup order
+// sum_n grad_a_src[n,h] xp[n,h,c] | sum_n grad_a_dst[n,h] xp[n,h,c], which the reducer adds in workgroup order into
+// grad_att [2, H * C] or, split, into an [H, 2C] table with the source half at [:, C:]
 int gat_att_blocks(int64_t N);
 int launch_gat_scores(const float *xp, int64_t ld, const float *att_src, const float *att_dst, int64_t lda, int64_t N,
                       int H, int C, float *a_src, float *a_dst, hipStream_t st);
 int launch_gat_att_part(const float *xp, int64_t ld, const float *gasrc, const float *gadst, int64_t N, int H, int C,
                         double *part, hipStream_t st);
+int launch_gat_att_red(const double *part, int64_t N, int H, int C, bool split, float *grad_att, hipStream_t st);
 
 bool kept_bits_path(const sngnn_graph_t *g, int top_k);
 bool fwd_scores_on_the_fly_forced();          // agg_fwd.hip (knob 2 == 2)     // agg_bwd.hip: forward-written kept bits usable

@@ -71,6 +71,23 @@ __device__ __forceinline__ double wave_sum_d(double v)
     return v;
 }
 
+// Maximum and sum over the P lanes of an aligned cohort (P a power of two), by an xor butterfly; every lane gets it.
+template <int P> __device__ __forceinline__ float cohort_max(float v)
+{
+#pragma unroll
+    for (int s = P / 2; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
+    return v;
+}
+// (each step adds a pair as a + b in one lane and b + a in the other: every lane ends with the same bits)
+template <int P> __device__ __forceinline__ float cohort_sum(float v)
+{
+#pragma unroll
+    for (int s = P / 2; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+
+__device__ __forceinline__ float leaky(float a, float slope) { return a > 0.f ? a : a * slope; }
+
 // Orders LDS traffic between the lanes of ONE wave (DS ops of a wave execute in
 // issue order; the fences stop the compiler from moving LDS accesses across).  The
 // fences name the LDS address space only: an all-address-space fence would also drain

@@ -37,6 +37,15 @@ template <class A> void bind_side(const sngnn_graph_t *g, bool csc, A &a)
     }
 }
 
+// bind_side for the edge-softmax families (gat.hip, wrgat.hip): their passes also need N and, to write an in-edge's record
+// where the out-edge pass reads it, the CSR -> CSC positions
+template <class A> void bind_softmax_side(const sngnn_graph_t *g, bool csc, A &a)
+{
+    a.N = (int)g->N;
+    a.csc_pos = g->csc_pos;
+    bind_side(g, csc, a);
+}
+
 // The graph part of BwdArgs (agg_bwd_impl.h; B = BwdArgs): both sides of the graph and the scratch regions of L
 // inside the workspace.  What depends on the mode stays with the caller, set explicitly: the rows (h, gout, wsel,
 // grad_h), wd / kmask / kmask_words / inv_deg / rec_dot, mode / top_k / role_mask / s_small_end, the fused-node
@@ -118,6 +127,13 @@ template <typename F> int dispatch_vec(const RowCfg &cfg, F &&f)
     default: return f(std::integral_constant<int, 4>{});
     }
 }
+
+// static int NAME(cfg, a, st): return FN<VEC, G, R>(a, st) for the row configuration (FN takes the ARGS by value)
+#define SNGNN_DEFINE_DISPATCH(NAME, FN, ARGS)                                                                          \
+    static int NAME(const RowCfg &cfg, const ARGS &a, hipStream_t st)                                                  \
+    {                                                                                                                  \
+        return dispatch_vec(cfg, [&](auto vec) { SNGNN_DISPATCH_GR(FN, decltype(vec)::value, cfg, a, st) });          \
+    }
 
 // f(VEC, G, R as integral constants) for a hop on a column slice: the lane layouts are row_cfg(W)'s, and - where the
 // slice's alignment forces a narrower vector than W's own - the same groups with 2 or 4 times the steps

@@ -1,4 +1,4 @@
-// Graph attention (PyG 2.0.4 GATConv's propagate) on the row classes of common.h (gfx950, fp32, one GPU).
+// Graph attention (PyG 2.0.4 GATConv's propagate) on the row classes of row_walk.h (gfx950, fp32, one GPU).
 //     xp [N, H, C] = lin_src(x),   a_src[n,h] = <xp[n,h,:], att_src[h,:]>,   a_dst alike
 //     per in-edge e = (j -> i) and head h:   a_e = leaky_relu(a_src[j,h] + a_dst[i,h])
 //     alpha_e = exp(a_e - m_i) / (l_i + 1e-16),   m_i = max_e a_e,   l_i = sum_e exp(a_e - m_i)
@@ -16,6 +16,9 @@
 //   split rows               128-edge wave tasks that write the partial row sum_e exp(a_e - m_t) xp_j, m_t and l_t;
 //                            the finalize merges them in task order: m = max m_t, l = sum l_t exp(m_t - m),
 //                            out = (sum_t exp(m_t - m) partial_t) / l
+// Which row or task a wave or lane group serves is row_walk.h's row_unit (k_gat_fwd, k_gat_bwd_t, k_gat_bwd_s; wrgat.hip's
+// kernels call it too): a dead unit runs the two passes over an empty range, so the cohort reductions between them are
+// never taken under divergence.
 // Every sum has a fixed order; there is no floating-point atomic and no host synchronisation.
 //
 // Backward from G = grad_out [N, H, C], saved: out, m, l (and the scores [N, H]):
@@ -26,15 +29,15 @@
 //                        grad_xp[j,h,:] += grad_a_src[j,h] att_src[h,:] + grad_a_dst[j,h] att_dst[h,:]
 //   grad_att_src[h,c] = sum_j grad_a_src[j,h] xp[j,h,c] (grad_att_dst alike): per-workgroup partials in double,
 //                        added in a fixed order by a reducer launch
-#include "device_utils.h"
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
 constexpr int GAT_MAX_HEADS = 16;
 constexpr int GAT_ATT_BLOCKS = 512;      // most workgroups (= partial results) of the grad_att reduction
 
-struct GatArgs {
+struct GatArgs : RowSide {         // the in-edges (forward, pass T) or the out-edges (pass S): row_walk.h
     const float *xp;               // [N, H, C]
     const float *gout;             // [N, H, C] backward: grad_out
     const float *fout;             // [N, H, C] backward: the forward's output
@@ -48,27 +51,8 @@ struct GatArgs {
     const float *att_src, *att_dst;    // [H, C]
     float slope;
     int H, C, W, N;
-    const int32_t *ptr, *idx, *perm, *csc_pos;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
+    const int32_t *csc_pos;
 };
-
-__device__ __forceinline__ float gat_leaky(float a, float slope) { return a > 0.f ? a : a * slope; }
-
-template <int P> __device__ __forceinline__ float cohort_max(float v)
-{
-#pragma unroll
-    for (int s = P / 2; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
-    return v;
-}
-// (each step adds a pair as a + b in one lane and b + a in the other: every lane ends with the same bits)
-template <int P> __device__ __forceinline__ float cohort_sum(float v)
-{
-#pragma unroll
-    for (int s = P / 2; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
 
 // pass one of a row (or task): m = max a_e and l = sum exp(a_e - m) over its edges [e0, e1), shared by P lanes
 template <int P>
@@ -77,11 +61,11 @@ __device__ __forceinline__ void gat_stats(const GatArgs &a, int h, int qs, int e
 {
     float mx = -INFINITY;
     for (int t = e0 + p; t < e1; t += P)
-        mx = fmaxf(mx, gat_leaky(a.asrc[(size_t)a.idx[qs + t] * a.H + h] + adst, a.slope));
+        mx = fmaxf(mx, leaky(a.asrc[(size_t)a.idx[qs + t] * a.H + h] + adst, a.slope));
     mx = cohort_max<P>(mx);
     float s = 0.f;
     for (int t = e0 + p; t < e1; t += P)
-        s += expf(gat_leaky(a.asrc[(size_t)a.idx[qs + t] * a.H + h] + adst, a.slope) - mx);
+        s += expf(leaky(a.asrc[(size_t)a.idx[qs + t] * a.H + h] + adst, a.slope) - mx);
     m = mx;
     l = cohort_sum<P>(s);
 }
@@ -92,7 +76,7 @@ __device__ __forceinline__ void gat_gather(const GatArgs &a, int h, int qs, int 
                                            float adst, float m, Row<VEC, G, R> &acc)
 {
     using RowT = Row<VEC, G, R>;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
+    constexpr int U = gather_unroll(R);
     const float *base = a.xp + h * a.C;
     for (int b = e0 + first; b < e1; b += stride * U) {
         RowT x[U];
@@ -104,44 +88,12 @@ __device__ __forceinline__ void gat_gather(const GatArgs &a, int h, int qs, int 
             act[u] = t < e1;
             const int j = act[u] ? a.idx[qs + t] : 0;
             x[u].load(base + (size_t)j * a.W, a.C, lg);
-            w[u] = expf(gat_leaky(a.asrc[(size_t)j * a.H + h] + adst, a.slope) - m);
+            w[u] = expf(leaky(a.asrc[(size_t)j * a.H + h] + adst, a.slope) - m);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (act[u]) acc.axpy(w[u], x[u]);
     }
-}
-
-// which row (or task) a wave / lane group serves: the decode of k_prop
-struct GatUnit {
-    bool live, task;
-    int seg, tq, qs, e0, e1;
-};
-
-template <int G> __device__ __forceinline__ GatUnit gat_unit(const GatArgs &a, int b, int wave, int gid, bool &wide)
-{
-    constexpr int NG = 64 / G;
-    GatUnit u;
-    u.tq = 0;
-    wide = b < a.nbA + a.nbB;
-    if (wide) {
-        u.task = b < a.nbA;
-        u.tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        u.live = u.task ? u.tq < a.n_tasks : slot < a.n_med_end;               // (wave-uniform)
-        u.seg = u.live ? a.perm[u.task ? a.task_slot[u.tq] : slot] : 0;
-        u.e0 = u.live && u.task ? a.task_chunk[u.tq] * CHUNK : 0;
-    } else {
-        u.task = false;
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        u.live = slot < a.N;
-        u.seg = u.live ? a.perm[slot] : 0;
-        u.e0 = 0;
-    }
-    u.qs = a.ptr[u.seg];
-    const int deg = u.live ? a.ptr[u.seg + 1] - u.qs : 0;
-    u.e1 = u.task ? min(deg, u.e0 + CHUNK) : deg;
-    return u;
 }
 
 template <int VEC, int G, int R> __global__ __launch_bounds__(BLOCK) void k_gat_fwd(const GatArgs a)
@@ -152,7 +104,7 @@ template <int VEC, int G, int R> __global__ __launch_bounds__(BLOCK) void k_gat_
     const int gid = lane / G, lg = lane % G;
     const int h = blockIdx.y;
     bool wide;
-    const GatUnit u = gat_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const float adst = a.adst[(size_t)u.seg * a.H + h];
     RowT acc;
     acc.zero();
@@ -215,7 +167,7 @@ template <int VEC, int G, int R> __global__ __launch_bounds__(BLOCK) void k_gat_
     const int gid = lane / G, lg = lane % G;
     const int h = blockIdx.y;
     bool wide;
-    const GatUnit u = gat_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const size_t sh = (size_t)u.seg * a.H + h;
     const float adst = a.adst[sh], m = a.m[sh], l = a.l[sh];
     RowT gi, oi;
@@ -242,7 +194,7 @@ template <int VEC, int G, int R> __global__ __launch_bounds__(BLOCK) void k_gat_
         for (int q = 0; q < U; ++q) {
             const float te = group_sum<G>(gi.dot_partial(x[q]));
             const float raw = a.asrc[(size_t)j[q] * a.H + h] + adst;
-            const float alpha = expf(gat_leaky(raw, a.slope) - m) / l;
+            const float alpha = expf(leaky(raw, a.slope) - m) / l;
             const float ds = alpha * (te - dot);
             const float da = raw > 0.f ? ds : ds * a.slope;
             if (act[q]) {
@@ -276,12 +228,12 @@ template <int VEC, int G, int R> __global__ __launch_bounds__(BLOCK) void k_gat_
 {
     using RowT = Row<VEC, G, R>;
     constexpr int NG = 64 / G;
-    constexpr int U = 4 / (R >= 4 ? 4 : R);
+    constexpr int U = gather_unroll(R);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int gid = lane / G, lg = lane % G;
     const int h = blockIdx.y;
     bool wide;
-    const GatUnit u = gat_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const float *base = a.gout + h * a.C;
     const int stride = wide ? NG : 1, first = wide ? gid : 0;
     RowT acc;
@@ -392,72 +344,54 @@ static __global__ __launch_bounds__(256) void k_gat_att_part(const float *__rest
     }
 }
 
-// grad_att [2, W] = the partials added in workgroup order
-static __global__ __launch_bounds__(256) void k_gat_att_red(const double *__restrict__ part, int B, int W,
-                                                            float *__restrict__ gatt)
+// grad_att = the partials added in workgroup order: [2, H * C] (the source vector, then the target's), or - split - as
+// WRGAT's atten [H, 2C], whose source half is [:, C:]
+static __global__ __launch_bounds__(256) void k_gat_att_red(const double *__restrict__ part, int B, int H, int C,
+                                                            int split, float *__restrict__ gatt)
 {
+    const int W = H * C;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= 2 * W) return;
     const int which = i / W, c = i % W;
     double s = 0.0;
     for (int b = 0; b < B; ++b) s += part[((size_t)b * 2 + which) * W + c];
-    gatt[i] = (float)s;
+    gatt[split ? (size_t)(c / C) * 2 * C + (which == 0 ? C : 0) + c % C : i] = (float)s;
 }
 
-static void gat_side(const sngnn_graph_t *g, bool transpose, GatArgs &a)
+template <int VEC, int G, int R> int launch_gat_fwd(GatArgs a, hipStream_t st)
 {
-    a.N = (int)g->N;
-    a.csc_pos = g->csc_pos;
-    bind_side(g, transpose, a);
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-}
-
-template <int G> static dim3 gat_grid(const GatArgs &a)
-{
-    const int nbC = ceil_div(a.N - a.n_med_end, (int64_t)WAVES * (64 / G));
-    return dim3(a.nbA + a.nbB + nbC, a.H);
-}
-
-template <int VEC, int G, int R> int launch_gat_fwd(const GatArgs &a, hipStream_t st)
-{
-    const dim3 grid = gat_grid<G>(a);
-    if (grid.x > 0) k_gat_fwd<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
+    const int nb = plan_side(a, a.N, 64 / G);
+    if (nb > 0) k_gat_fwd<VEC, G, R><<<dim3(nb, a.H), BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_gat_fwd_fin<<<dim3(a.n_split, a.H), 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int R> int launch_gat_bwd_t(const GatArgs &a, hipStream_t st)
+template <int VEC, int G, int R> int launch_gat_bwd_t(GatArgs a, hipStream_t st)
 {
-    const dim3 grid = gat_grid<G>(a);
-    if (grid.x > 0) k_gat_bwd_t<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
+    const int nb = plan_side(a, a.N, 64 / G);
+    if (nb > 0) k_gat_bwd_t<VEC, G, R><<<dim3(nb, a.H), BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_gat_bwd_t_fin<<<a.n_split, 64, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int R> int launch_gat_bwd_s(const GatArgs &a, hipStream_t st)
+template <int VEC, int G, int R> int launch_gat_bwd_s(GatArgs a, hipStream_t st)
 {
-    const dim3 grid = gat_grid<G>(a);
-    if (grid.x > 0) k_gat_bwd_s<VEC, G, R><<<grid, BLOCK, 0, st>>>(a);
+    const int nb = plan_side(a, a.N, 64 / G);
+    if (nb > 0) k_gat_bwd_s<VEC, G, R><<<dim3(nb, a.H), BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_gat_bwd_s_fin<<<dim3(a.n_split, a.H), 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-#define GAT_DISPATCH(NAME, FN)                                                                                         \
-    static int NAME(const RowCfg &cfg, const GatArgs &a, hipStream_t st)                                               \
-    {                                                                                                                  \
-        return dispatch_vec(cfg, [&](auto vec) { SNGNN_DISPATCH_GR(FN, decltype(vec)::value, cfg, a, st) });          \
-    }
-GAT_DISPATCH(dispatch_gat_fwd, launch_gat_fwd)
-GAT_DISPATCH(dispatch_gat_bwd_t, launch_gat_bwd_t)
-GAT_DISPATCH(dispatch_gat_bwd_s, launch_gat_bwd_s)
+SNGNN_DEFINE_DISPATCH(dispatch_gat_fwd, launch_gat_fwd, GatArgs)
+SNGNN_DEFINE_DISPATCH(dispatch_gat_bwd_t, launch_gat_bwd_t, GatArgs)
+SNGNN_DEFINE_DISPATCH(dispatch_gat_bwd_s, launch_gat_bwd_s, GatArgs)
 
 static int gat_att_npb(int64_t N) { return (int)std::max<int64_t>(8, (N + GAT_ATT_BLOCKS - 1) / GAT_ATT_BLOCKS); }
 
-// (common.h: the score pass and the grad_att partials on rows ld floats apart - wrgat.hip enters them too)
+// (common.h: the score pass, the grad_att partials on rows ld floats apart and their reducer - wrgat.hip enters them too)
 int gat_att_blocks(int64_t N) { return ceil_div(std::max<int64_t>(N, 1), gat_att_npb(N)); }
 
 int launch_gat_scores(const float *xp, int64_t ld, const float *att_src, const float *att_dst, int64_t lda, int64_t N,
@@ -472,6 +406,13 @@ int launch_gat_att_part(const float *xp, int64_t ld, const float *gasrc, const f
                         double *part, hipStream_t st)
 {
     k_gat_att_part<<<gat_att_blocks(N), 256, 0, st>>>(xp, ld, gasrc, gadst, (int)N, H, C, gat_att_npb(N), part);
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+int launch_gat_att_red(const double *part, int64_t N, int H, int C, bool split, float *grad_att, hipStream_t st)
+{
+    k_gat_att_red<<<ceil_div(2 * H * C, 256), 256, 0, st>>>(part, gat_att_blocks(N), H, C, split, grad_att);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
@@ -538,7 +479,7 @@ extern "C" int sngnn_gat_forward(const sngnn_graph_t *g, const float *xp, const 
     SN_REQUIRE(rows_aligned(16, {xp, out, workspace}), SNGNN_EINVAL, "rows must be aligned to 16 bytes");
     const GatLayout L = gat_layout(g, H, C);
     GatArgs a = {};
-    gat_side(g, false, a);
+    bind_softmax_side(g, false, a);
     a.xp = xp; a.asrc = a_src; a.adst = a_dst; a.out = out;
     a.m = ml; a.l = ml + g->N * (int64_t)H;
     a.partial = (float *)workspace;
@@ -571,10 +512,10 @@ extern "C" int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out,
     a.gadst = (float *)((char *)workspace + L.gadst);
     a.att_src = att_src; a.att_dst = att_dst;
     a.slope = negative_slope; a.H = H; a.C = C; a.W = H * C;
-    gat_side(g, false, a);
+    bind_softmax_side(g, false, a);
     int rc = dispatch_gat_bwd_t(cfg, a, st);
     if (rc != SNGNN_OK) return rc;
-    gat_side(g, true, a);
+    bind_softmax_side(g, true, a);
     a.out = grad_xp;
     rc = dispatch_gat_bwd_s(cfg, a, st);
     if (rc != SNGNN_OK) return rc;
@@ -582,8 +523,7 @@ extern "C" int sngnn_gat_backward(const sngnn_graph_t *g, const float *grad_out,
         double *part = (double *)((char *)workspace + L.att);
         rc = launch_gat_att_part(xp, (int64_t)H * C, a.gasrc, a.gadst, g->N, H, C, part, st);
         if (rc != SNGNN_OK) return rc;
-        k_gat_att_red<<<ceil_div(2 * H * C, 256), 256, 0, st>>>(part, gat_att_blocks(g->N), H * C, grad_att);
-        SN_HIP(hipGetLastError());
+        return launch_gat_att_red(part, g->N, H, C, false, grad_att, st);
     }
     return SNGNN_OK;
 }

@@ -1,10 +1,12 @@
-// The row-class walk of the gather-sum hop kernels (gfx950, wave = 64), in one place: k_adj, k_prop, k_gcn_hop,
-// k_gcn2_hop, k_h2gcn_hop and k_acm are walk_rows with a family's gather, partial store and epilogue (k_glo_hop
-// shares the gather, the finalize sum and the launch plan, and spells the walk out: see glognn.hip).
+// The row-class walk (gfx950, wave = 64), in one place:
 //   split segments (deg > WAVE_T)   CHUNK-edge tasks, one wave each, the lane groups striding the task's edges; the
-//                                   tasks' partial rows are added by the family's finalize kernel (sum_task_partials)
+//                                   tasks' partial rows are merged by the family's finalize kernel
 //   wave segments  (deg > SMALL_T)  one wave each, the lane groups striding the edges
 //   small segments                  one G-lane group each
+// Two ways onto it.  The gather-sum hop kernels - k_adj, k_prop, k_gcn_hop, k_gcn2_hop, k_h2gcn_hop and k_acm - are
+// walk_rows with a family's gather, partial store and epilogue (k_glo_hop shares the gather, the finalize sum and the
+// launch plan, and spells the walk out: see glognn.hip).  The edge-softmax kernels of gat.hip and wrgat.hip pass over a
+// unit twice and reduce across lanes in between: they call the decode row_unit and keep their own bodies.
 // Contract ("The row-class walker"): every sum's order is fixed by G, CHUNK and the graph alone; no atomics.
 #pragma once
 #include "device_utils.h"
@@ -13,7 +15,7 @@ namespace sngnn {
 
 // One side of a graph as a kernel walks it (bind_side, entry.h): the segments (CSR by target or CSC by source), the
 // gathered ids, the degree order, the row classes with the split segments' tasks, and the launch's workgroup counts
-// (plan_side).  The args struct of every kernel on walk_rows derives from it.
+// (plan_side).  The args struct of every kernel on walk_rows or row_unit derives from it.
 struct RowSide {
     const int32_t *ptr, *idx, *perm;
     int n_split, n_med_end, n_tasks;
@@ -21,7 +23,49 @@ struct RowSide {
     int nbA, nbB;               // workgroups of split tasks and of wave segments, in front of the small segments'
 };
 
-// Workgroup b of a side with N segments.  acc: the per-row state, any type with zero() and reduce_across_groups() (a
+// Which segment (or task) of a side with N segments a wave / lane group of workgroup b serves, for kernels that keep their
+// own body.  G is the lane-group width of the SMALL segments only (a scalar pass calls it with the width it gives such a
+// segment, whatever its rows' layout); gid = lane / G.
+//   wide   wave-uniform: a task or a wave segment - all 64 lanes share [e0, e1); otherwise a small segment a group
+//   task   the unit is task tq, the entries [e0, e1) of its segment; otherwise the whole segment, e0 = 0
+//   qs     where the segment's entries start in idx: entry t is idx[qs + t]
+// A dead unit (a wave past the tasks or wave segments, a group past the last segment) comes back as live = false, seg = 0,
+// qs = ptr[0], e0 = e1 = 0: every lane then runs the caller's loops - over an empty range - and its shuffles, so a cross-
+// lane reduction is never taken under divergence; `live` guards the stores alone.
+struct RowUnit {
+    bool live, task;
+    int seg, tq, qs, e0, e1;
+};
+
+template <int G> __device__ __forceinline__ RowUnit row_unit(const RowSide &s, int N, int b, int wave, int gid, bool &wide)
+{
+    constexpr int NG = 64 / G;
+    RowUnit u;
+    u.tq = 0;
+    wide = b < s.nbA + s.nbB;
+    if (wide) {
+        u.task = b < s.nbA;
+        u.tq = b * WAVES + wave;
+        const int slot = s.n_split + (b - s.nbA) * WAVES + wave;
+        u.live = u.task ? u.tq < s.n_tasks : slot < s.n_med_end;               // (wave-uniform)
+        u.seg = u.live ? s.perm[u.task ? s.task_slot[u.tq] : slot] : 0;
+        u.e0 = u.live && u.task ? s.task_chunk[u.tq] * CHUNK : 0;
+    } else {
+        u.task = false;
+        const int slot = s.n_med_end + ((b - s.nbA - s.nbB) * WAVES + wave) * NG + gid;
+        u.live = slot < N;
+        u.seg = u.live ? s.perm[slot] : 0;
+        u.e0 = 0;
+    }
+    u.qs = s.ptr[u.seg];
+    const int deg = u.live ? s.ptr[u.seg + 1] - u.qs : 0;
+    u.e1 = u.task ? min(deg, u.e0 + CHUNK) : deg;
+    return u;
+}
+
+// Workgroup b of a side with N segments, for a gather-sum.  It keeps its own decode, in which a lane without work calls
+// nothing: written over row_unit it cost k_acm<4, 16, 1>, k_acm<4, 32, 1> and k_adj<2, 64, 8> a wave of occupancy
+// (profiles/row_walk_resources.txt).  acc: the per-row state, any type with zero() and reduce_across_groups() (a
 // Row, or ACM's pair of them).
 //   gather(seg, qs, e0, e1, stride, first, lg, acc)   acc += the entries e0 + first, + stride, ... < e1 of segment seg,
 //                                                     whose entries start at qs

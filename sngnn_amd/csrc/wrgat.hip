@@ -1,5 +1,5 @@
 // Weighted relational graph attention (models.py:1903-2014, WeightedRGATConv after its linear maps) on the row classes
-// of common.h (gfx950, fp32, one GPU).  Edges carry a relation r in [0, R) and a weight w:
+// of row_walk.h (gfx950, fp32, one GPU).  Edges carry a relation r in [0, R) and a weight w:
 //     P [N, R, C],  P[n,r,:] = x[n] W_r,   s_dst[n,r] = <P[n,r], atten[r,:C]>,   s_src[n,r] = <P[n,r], atten[r,C:]>
 //     per in-edge e = (j -> i, r, w):   raw_e = s_dst[i,r] + s_src[j,r],   a_e = leaky_relu(raw_e)
 //     per segment (i, r) of n_ir edges: m = max a_e,  l = sum exp(a_e - m),  alpha_e = exp(a_e - m) / l
@@ -26,17 +26,19 @@
 //   pass S (out-edges)  relations on gridDim.y: a workgroup serves one relation of its sources, reads every record and
 //                       gathers G_i for the entries of its relation only: grad_P[j,r,:] = sum c_e G_i, grad_s_src[j,r] =
 //                       sum da_e, and in the store += grad_s_src[j,r] atten[r,C:] + grad_s_dst[j,r] atten[r,:C]
-//   grad_atten          gat.hip's per-workgroup partials in double, added in workgroup order; grad_bias alike
-// Every sum has a fixed order; no floating-point atomic, no host synchronisation.
-#include "device_utils.h"
+//   grad_atten          gat.hip's per-workgroup partials in double and its reducer (workgroup order); grad_bias alike
+// All six row-class kernels (k_wr_stats, k_wr_fwd, k_wr_bwd_t, k_wr_bwd_d, k_wr_bwd_rec, k_wr_bwd_s) decode their unit with
+// row_walk.h's row_unit - the scalar passes at WR_SG lanes a small row -, the cohort reductions and leaky are
+// device_utils.h's.  Every sum has a fixed order; no floating-point atomic, no host synchronisation.
 #include "entry.h"
+#include "row_walk.h"
 
 namespace sngnn {
 
 constexpr int WR_MAX_REL = 16;
 constexpr int WR_SG = 16;                // lanes of a small row in the scalar passes (one per entry)
 
-struct WrArgs {
+struct WrArgs : RowSide {          // the in-edges or, in pass S, the out-edges: row_walk.h
     const float *P;                // [N, R, C], rows ldp floats apart
     int64_t ldp;
     const float *self;             // forward: the root slice [N, C] (rows lds apart) or nullptr
@@ -60,27 +62,8 @@ struct WrArgs {
     float slope;
     int relu;
     int R, C, N;
-    const int32_t *ptr, *idx, *perm, *csc_pos;
-    int n_split, n_med_end, n_tasks;
-    const int32_t *task_slot, *task_chunk, *split_task0;
-    int nbA, nbB;
+    const int32_t *csc_pos;
 };
-
-__device__ __forceinline__ float wr_leaky(float a, float slope) { return a > 0.f ? a : a * slope; }
-
-template <int P> __device__ __forceinline__ float wr_max(float v)
-{
-#pragma unroll
-    for (int s = P / 2; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
-    return v;
-}
-// (each step adds a pair as a + b in one lane and b + a in the other: every lane ends with the same bits)
-template <int P> __device__ __forceinline__ float wr_sum(float v)
-{
-#pragma unroll
-    for (int s = P / 2; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
 
 // the relation of entry t of a row: the last r with rp[r] <= t (empty segments in between are skipped)
 __device__ __forceinline__ int wr_rel(const int32_t *__restrict__ rp, int R, int t)
@@ -94,43 +77,11 @@ __device__ __forceinline__ int wr_rel(const int32_t *__restrict__ rp, int R, int
     return lo;
 }
 
-// which row (or task) a wave / lane group serves
-struct WrUnit {
-    bool live, task;
-    int seg, tq, qs, e0, e1;
-};
-
-template <int G> __device__ __forceinline__ WrUnit wr_unit(const WrArgs &a, int b, int wave, int gid, bool &wide)
-{
-    constexpr int NG = 64 / G;
-    WrUnit u;
-    u.tq = 0;
-    wide = b < a.nbA + a.nbB;
-    if (wide) {
-        u.task = b < a.nbA;
-        u.tq = b * WAVES + wave;
-        const int slot = a.n_split + (b - a.nbA) * WAVES + wave;
-        u.live = u.task ? u.tq < a.n_tasks : slot < a.n_med_end;               // (wave-uniform)
-        u.seg = u.live ? a.perm[u.task ? a.task_slot[u.tq] : slot] : 0;
-        u.e0 = u.live && u.task ? a.task_chunk[u.tq] * CHUNK : 0;
-    } else {
-        u.task = false;
-        const int slot = a.n_med_end + ((b - a.nbA - a.nbB) * WAVES + wave) * NG + gid;
-        u.live = slot < a.N;
-        u.seg = u.live ? a.perm[slot] : 0;
-        u.e0 = 0;
-    }
-    u.qs = a.ptr[u.seg];
-    const int deg = u.live ? a.ptr[u.seg + 1] - u.qs : 0;
-    u.e1 = u.task ? min(deg, u.e0 + CHUNK) : deg;
-    return u;
-}
-
 // alpha_e of entry t of segment (seg, r)
 __device__ __forceinline__ float wr_alpha(const WrArgs &a, size_t sr, int j, int r, float sd, float &raw)
 {
     raw = a.ssrc[(size_t)j * a.R + r] + sd;
-    return expf(wr_leaky(raw, a.slope) - a.m[sr]) / a.l[sr];
+    return expf(leaky(raw, a.slope) - a.m[sr]) / a.l[sr];
 }
 
 // ---- forward: statistics ---------------------------------------------------------------------------------------------
@@ -138,7 +89,7 @@ static __global__ __launch_bounds__(BLOCK) void k_wr_stats(const WrArgs a)
 {
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     bool wide;
-    const WrUnit u = wr_unit<WR_SG>(a, blockIdx.x, wave, lane / WR_SG, wide);
+    const RowUnit u = row_unit<WR_SG>(a, a.N, blockIdx.x, wave, lane / WR_SG, wide);
     const int32_t *rp = a.rel_ptr + (size_t)u.seg * (a.R + 1);
     const int P = wide ? 64 : WR_SG, p = wide ? lane : lane % WR_SG;
     for (int r = 0; r < a.R; ++r) {                                            // (R is uniform: the butterflies converge)
@@ -146,12 +97,12 @@ static __global__ __launch_bounds__(BLOCK) void k_wr_stats(const WrArgs a)
         const float sd = a.sdst[(size_t)u.seg * a.R + r];
         float mx = -INFINITY;
         for (int t = s0 + p; t < s1; t += P)
-            mx = fmaxf(mx, wr_leaky(a.ssrc[(size_t)a.idx[u.qs + t] * a.R + r] + sd, a.slope));
-        mx = wide ? wr_max<64>(mx) : wr_max<WR_SG>(mx);
+            mx = fmaxf(mx, leaky(a.ssrc[(size_t)a.idx[u.qs + t] * a.R + r] + sd, a.slope));
+        mx = wide ? cohort_max<64>(mx) : cohort_max<WR_SG>(mx);
         float s = 0.f;
         for (int t = s0 + p; t < s1; t += P)
-            s += expf(wr_leaky(a.ssrc[(size_t)a.idx[u.qs + t] * a.R + r] + sd, a.slope) - mx);
-        s = wide ? wr_sum<64>(s) : wr_sum<WR_SG>(s);
+            s += expf(leaky(a.ssrc[(size_t)a.idx[u.qs + t] * a.R + r] + sd, a.slope) - mx);
+        s = wide ? cohort_sum<64>(s) : cohort_sum<WR_SG>(s);
         if (u.live && p == 0) {
             if (u.task) {
                 a.ts[((size_t)u.tq * a.R + r) * 3] = mx;
@@ -187,11 +138,11 @@ template <int VEC, int G, int RR> __global__ __launch_bounds__(BLOCK) void k_wr_
 {
     using RowT = Row<VEC, G, RR>;
     constexpr int NG = 64 / G;
-    constexpr int U = 4 / (RR >= 4 ? 4 : RR);
+    constexpr int U = gather_unroll(RR);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int gid = lane / G, lg = lane % G;
     bool wide;
-    const WrUnit u = wr_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const int32_t *rp = a.rel_ptr + (size_t)u.seg * (a.R + 1);
     const int stride = wide ? NG : 1, first = wide ? gid : 0;
     RowT acc;
@@ -279,7 +230,7 @@ template <int VEC, int G, int RR> __global__ __launch_bounds__(BLOCK) void k_wr_
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int gid = lane / G, lg = lane % G;
     bool wide;
-    const WrUnit u = wr_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const int32_t *rp = a.rel_ptr + (size_t)u.seg * (a.R + 1);
     RowT gi;
     gi.load(a.g + (size_t)u.seg * a.ldg, a.C, lg);
@@ -310,7 +261,7 @@ static __global__ __launch_bounds__(BLOCK) void k_wr_bwd_d(const WrArgs a)
 {
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     bool wide;
-    const WrUnit u = wr_unit<WR_SG>(a, blockIdx.x, wave, lane / WR_SG, wide);
+    const RowUnit u = row_unit<WR_SG>(a, a.N, blockIdx.x, wave, lane / WR_SG, wide);
     const int32_t *rp = a.rel_ptr + (size_t)u.seg * (a.R + 1);
     const int P = wide ? 64 : WR_SG, p = wide ? lane : lane % WR_SG;
     for (int r = 0; r < a.R; ++r) {
@@ -327,8 +278,8 @@ static __global__ __launch_bounds__(BLOCK) void k_wr_bwd_d(const WrArgs a)
             B += al * wt;
             K += al;
         }
-        if (wide) { A = wr_sum<64>(A); B = wr_sum<64>(B); K = wr_sum<64>(K); }
-        else { A = wr_sum<WR_SG>(A); B = wr_sum<WR_SG>(B); K = wr_sum<WR_SG>(K); }
+        if (wide) { A = cohort_sum<64>(A); B = cohort_sum<64>(B); K = cohort_sum<64>(K); }
+        else { A = cohort_sum<WR_SG>(A); B = cohort_sum<WR_SG>(B); K = cohort_sum<WR_SG>(K); }
         if (u.live && p == 0) {
             if (u.task) {
                 float *ts = a.ts + ((size_t)u.tq * a.R + r) * 3;
@@ -363,7 +314,7 @@ static __global__ __launch_bounds__(BLOCK) void k_wr_bwd_rec(const WrArgs a)
 {
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     bool wide;
-    const WrUnit u = wr_unit<WR_SG>(a, blockIdx.x, wave, lane / WR_SG, wide);
+    const RowUnit u = row_unit<WR_SG>(a, a.N, blockIdx.x, wave, lane / WR_SG, wide);
     if (!u.live) return;
     const int32_t *rp = a.rel_ptr + (size_t)u.seg * (a.R + 1);
     const int P = wide ? 64 : WR_SG, p = wide ? lane : lane % WR_SG;
@@ -387,12 +338,12 @@ template <int VEC, int G, int RR> __global__ __launch_bounds__(BLOCK) void k_wr_
 {
     using RowT = Row<VEC, G, RR>;
     constexpr int NG = 64 / G;
-    constexpr int U = 4 / (RR >= 4 ? 4 : RR);
+    constexpr int U = gather_unroll(RR);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int gid = lane / G, lg = lane % G;
     const int r = blockIdx.y;
     bool wide;
-    const WrUnit u = wr_unit<G>(a, blockIdx.x, wave, gid, wide);
+    const RowUnit u = row_unit<G>(a, a.N, blockIdx.x, wave, gid, wide);
     const int stride = wide ? NG : 1, first = wide ? gid : 0;
     RowT acc;
     acc.zero();
@@ -460,20 +411,6 @@ static __global__ __launch_bounds__(256) void k_wr_bwd_s_fin(const WrArgs a)
     }
 }
 
-// grad_atten [R, 2C] = gat.hip's partials [B, 2, R * C] (grad_s_src's, then grad_s_dst's) added in workgroup order:
-// the source half is atten[:, C:]
-static __global__ __launch_bounds__(256) void k_wr_att_red(const double *__restrict__ part, int B, int R, int C,
-                                                           float *__restrict__ gatt)
-{
-    const int W = R * C;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 2 * W) return;
-    const int which = i / W, rc = i % W;
-    double s = 0.0;
-    for (int b = 0; b < B; ++b) s += part[((size_t)b * 2 + which) * W + rc];
-    gatt[(size_t)(rc / C) * 2 * C + (which == 0 ? C : 0) + rc % C] = (float)s;
-}
-
 // grad_bias: workgroup b's column sums over its npb rows, in double; then the partials in workgroup order
 static __global__ __launch_bounds__(256) void k_wr_bias_part(const float *__restrict__ g, int64_t ldg, int N, int C,
                                                              int npb, double *__restrict__ part)
@@ -497,54 +434,35 @@ static __global__ __launch_bounds__(256) void k_wr_bias_red(const double *__rest
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-static void wr_side(const sngnn_graph_t *g, bool transpose, WrArgs &a)
+template <int VEC, int G, int RR> int launch_wr_fwd(WrArgs a, hipStream_t st)
 {
-    a.N = (int)g->N;
-    a.csc_pos = g->csc_pos;
-    bind_side(g, transpose, a);
-    a.nbA = ceil_div(a.n_tasks, WAVES);
-    a.nbB = ceil_div(a.n_med_end - a.n_split, WAVES);
-}
-
-static int wr_blocks(const WrArgs &a, int G)
-{
-    return a.nbA + a.nbB + ceil_div(a.N - a.n_med_end, (int64_t)WAVES * (64 / G));
-}
-
-template <int VEC, int G, int RR> int launch_wr_fwd(const WrArgs &a, hipStream_t st)
-{
-    const int nb = wr_blocks(a, G);
+    const int nb = plan_side(a, a.N, 64 / G);
     if (nb > 0) k_wr_fwd<VEC, G, RR><<<nb, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_wr_fwd_fin<<<a.n_split, 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int RR> int launch_wr_bwd_t(const WrArgs &a, hipStream_t st)
+template <int VEC, int G, int RR> int launch_wr_bwd_t(WrArgs a, hipStream_t st)
 {
-    const int nb = wr_blocks(a, G);
+    const int nb = plan_side(a, a.N, 64 / G);
     if (nb > 0) k_wr_bwd_t<VEC, G, RR><<<nb, BLOCK, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int RR> int launch_wr_bwd_s(const WrArgs &a, hipStream_t st)
+template <int VEC, int G, int RR> int launch_wr_bwd_s(WrArgs a, hipStream_t st)
 {
-    const int nb = wr_blocks(a, G);
+    const int nb = plan_side(a, a.N, 64 / G);
     if (nb > 0) k_wr_bwd_s<VEC, G, RR><<<dim3(nb, a.R), BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_wr_bwd_s_fin<<<dim3(a.n_split, a.R), 256, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }
 
-#define WR_DISPATCH(NAME, FN)                                                                                          \
-    static int NAME(const RowCfg &cfg, const WrArgs &a, hipStream_t st)                                                \
-    {                                                                                                                  \
-        return dispatch_vec(cfg, [&](auto vec) { SNGNN_DISPATCH_GR(FN, decltype(vec)::value, cfg, a, st) });          \
-    }
-WR_DISPATCH(dispatch_wr_fwd, launch_wr_fwd)
-WR_DISPATCH(dispatch_wr_bwd_t, launch_wr_bwd_t)
-WR_DISPATCH(dispatch_wr_bwd_s, launch_wr_bwd_s)
+SNGNN_DEFINE_DISPATCH(dispatch_wr_fwd, launch_wr_fwd, WrArgs)
+SNGNN_DEFINE_DISPATCH(dispatch_wr_bwd_t, launch_wr_bwd_t, WrArgs)
+SNGNN_DEFINE_DISPATCH(dispatch_wr_bwd_s, launch_wr_bwd_s, WrArgs)
 
 // workspace regions (256-byte aligned): the tasks' partial rows of either side | three scalars per task and relation |
 // t_e | the records | D, grad_s_src, grad_s_dst | the masked G of a layer without a root slice | the f64 partials of
@@ -611,7 +529,7 @@ extern "C" int sngnn_wrgat_forward(const sngnn_graph_t *g, const float *P, int64
     const WrLayout L = wr_layout(g, R, C);
     const int64_t NR = g->N * (int64_t)R;
     WrArgs a = {};
-    wr_side(g, false, a);
+    bind_softmax_side(g, false, a);
     a.P = P; a.ldp = P_stride; a.self = self_rows; a.lds = self_stride; a.bias = bias;
     a.out = out; a.ldo = C;
     a.ssrc = scores; a.sdst = scores + NR; a.m = ml; a.l = ml + NR;
@@ -620,7 +538,7 @@ extern "C" int sngnn_wrgat_forward(const sngnn_graph_t *g, const float *P, int64
     a.slope = negative_slope; a.relu = relu; a.R = R; a.C = C;
     int rc = launch_gat_scores(P, P_stride, atten + C, atten, 2 * (int64_t)C, g->N, R, C, scores, scores + NR, st);
     if (rc != SNGNN_OK) return rc;
-    const int nb = wr_blocks(a, WR_SG);
+    const int nb = plan_side(a, a.N, 64 / WR_SG);
     if (nb > 0) k_wr_stats<<<nb, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_wr_stats_fin<<<a.n_split, 64, 0, st>>>(a);
     SN_HIP(hipGetLastError());
@@ -673,15 +591,15 @@ extern "C" int sngnn_wrgat_backward(const sngnn_graph_t *g, const float *grad_ou
     }
     SN_HIP(hipGetLastError());
     if (!grad_P && !grad_atten) return SNGNN_OK;
-    wr_side(g, false, a);
+    bind_softmax_side(g, false, a);
     int rc = dispatch_wr_bwd_t(cfg, a, st);
     if (rc != SNGNN_OK) return rc;
-    const int nb = wr_blocks(a, WR_SG);
+    const int nb = plan_side(a, a.N, 64 / WR_SG);
     if (nb > 0) k_wr_bwd_d<<<nb, BLOCK, 0, st>>>(a);
     if (a.n_split > 0) k_wr_bwd_d_fin<<<a.n_split, 64, 0, st>>>(a);
     if (nb > 0) k_wr_bwd_rec<<<nb, BLOCK, 0, st>>>(a);
     SN_HIP(hipGetLastError());
-    wr_side(g, true, a);
+    bind_softmax_side(g, true, a);
     a.out = grad_P; a.ldo = grad_P_stride;
     rc = dispatch_wr_bwd_s(cfg, a, st);
     if (rc != SNGNN_OK) return rc;
@@ -689,8 +607,7 @@ extern "C" int sngnn_wrgat_backward(const sngnn_graph_t *g, const float *grad_ou
         double *part = (double *)((char *)workspace + L.att);
         rc = launch_gat_att_part(P, P_stride, a.gsrc, a.gdst, g->N, R, C, part, st);
         if (rc != SNGNN_OK) return rc;
-        k_wr_att_red<<<ceil_div(2 * R * C, 256), 256, 0, st>>>(part, B, R, C, grad_atten);
-        SN_HIP(hipGetLastError());
+        return launch_gat_att_red(part, g->N, R, C, true, grad_atten, st);      // (the source half is atten[:, C:])
     }
     return SNGNN_OK;
 }

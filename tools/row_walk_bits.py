@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The bits of the gather-sum hop kernels (csrc/row_walk.h and the seven kernels on it): one line per case - the case's
+"""The bits of the kernels on csrc/row_walk.h - the seven gather-sum hop kernels on walk_rows and the nine edge-softmax
+kernels of GAT and WRGAT on row_unit: one line per case - the case's
 name, then the sha256 of each output's bytes, forward and backward where the operator has one.  Inputs come from seeded
 CPU generators, so two builds of the library can be compared line for line:
 
@@ -14,7 +15,11 @@ needs it (loops replaced, raw, unique and loop-free).  Cases: gpr_propagate / ap
 47, h2gcn_conv at 6 and 40, glognn_norm at 5 and 40 (two orders), the ACM layer at 5 and 40 with and without relu,
 adj_linear forward and backward with bias at 40 (the lowest source id of either graph's SN edge list is above 0: the
 shifted rows and the bias-only tail run), once more without the sources below 3, and a weighted gather-sum (GGCN's
-plain propagation) at 40."""
+plain propagation) at 40.  The softmax families, on every lane layout their tests reach: gat_propagate at GAT_SHAPES
+(out, the saved m | l, grad_xp, grad_att_src, grad_att_dst), and wrgat_conv at WRGAT_SHAPES on the graph with one
+explicit loop per node but the last seven (relations wrgat_ref.scattered; TypedAdjacency sorts by relation), with and
+without edge weights, the root slice (and bias) and the fused relu (out, the saved m | l, grad_P, grad_atten, grad_self,
+grad_bias).  The hub's 18 tasks on either side run the three families' task-order merges."""
 import hashlib
 import math
 import os
@@ -25,7 +30,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tests import acm_ref, glognn_ref       # noqa: E402
+from tests import acm_ref, glognn_ref, wrgat_ref       # noqa: E402
 from tests import gpr_ref as R              # noqa: E402
 
 
@@ -45,6 +50,18 @@ def gen_for(name):
 
 def randn(gen, *shape):
     return torch.randn(*shape, generator=gen)
+
+
+def saved(out, function, index):
+    """A tensor the fused autograd function saved for its backward (the softmax's m and l [2, N, H]); read before
+    ``backward`` frees it.  The plain op sequence has no such node: the tool is about the kernels."""
+    assert type(out.grad_fn).__name__.startswith(function), "the fused arm"
+    return out.grad_fn.saved_tensors[index]
+
+
+# the (heads, C) and (R, C) pairs of tests/test_gat_gpu.py and tests/test_wrgat_gpu.py: SHAPES, then the other lane layouts
+GAT_SHAPES = ((1, 1), (1, 40), (2, 5), (2, 64), (3, 7), (4, 33), (8, 8), (1, 130), (2, 96), (1, 257), (1, 512), (16, 32))
+WRGAT_SHAPES = ((1, 1), (1, 40), (2, 5), (3, 7), (4, 33), (5, 8), (4, 64), (16, 32), (1, 130), (2, 96), (1, 257), (1, 512))
 
 
 def main():
@@ -144,6 +161,34 @@ def main():
         out = ops.weighted_propagate(x, wq, loops, aux)
         out.backward(randn(gen, n, c).to(dev))
         emit(name, out, x.grad, wq.grad)
+        for heads, c in GAT_SHAPES:
+            name = f"{gname} gat H={heads} C={c}"
+            gen = gen_for(name)
+            xp, g = randn(gen, n, heads * c).to(dev).requires_grad_(True), randn(gen, n, heads * c).to(dev)
+            ws, wd = (randn(gen, 1, heads, c).to(dev).requires_grad_(True) for _ in range(2))
+            out = ops.gat_propagate(xp, ws, wd, loops, heads)
+            ml = saved(out, "_GATPropagate", 4)
+            out.backward(g)
+            emit(name, out, ml, xp.grad, ws.grad, wd.grad)
+        # the typed graph of tests/test_wrgat_gpu.py: one explicit loop per node but the last seven (the build adds none)
+        nl = torch.arange(n - 7, dtype=torch.int64)
+        typed = torch.cat([ei, torch.stack([nl, nl])], dim=1).contiguous()
+        ew = wrgat_ref.weights(typed.size(1), gen_for(f"{gname} wrgat weights"))
+        for r, c in WRGAT_SHAPES:
+            et = wrgat_ref.scattered(typed, r)
+            for weighted in (True, False):
+                adj = ops.TypedAdjacency(typed.to(dev), et.to(dev), ew.to(dev) if weighted else None, n, r)
+                for root in (True, False):
+                    for relu in (True, False):
+                        name = f"{gname} wrgat R={r} C={c} w={int(weighted)} root={int(root)} relu={int(relu)}"
+                        gen = gen_for(name)
+                        p, atten = randn(gen, n, r * c), randn(gen, r, 2 * c) / math.sqrt(c)
+                        extras = (randn(gen, n, c), randn(gen, c)) if root else (None, None)
+                        ins = [None if t is None else t.to(dev).requires_grad_(True) for t in (p, atten) + extras]
+                        out = ops.wrgat_conv(*ins, adj, relu)
+                        ml = saved(out, "_WRGATConv", 3)
+                        out.backward(randn(gen, n, c).to(dev))
+                        emit(name, out, ml, *[None if t is None else t.grad for t in ins])
     torch.cuda.synchronize()
 
 
