@@ -32,6 +32,9 @@ def lib():
         _lib.sno_aggregate.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                        C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.sno_topk_weights.restype = None
+        _lib.sno_topk_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                                          C.c_void_p, C.c_void_p]
         _lib.sno_adj_linear.restype = None
         _lib.sno_adj_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
@@ -63,6 +66,12 @@ def aggregate(h: np.ndarray, edge_index: np.ndarray, *, add_loops=True, remove_l
                ei=np.stack([eo[:Ep], eo[Ep:2 * Ep]]))
     if sel is not None:
         res["sel_src"] = sel
+        # the chosen edge positions as well (sno_topk_weights on the returned cosines: the call sno_aggregate made)
+        dst = np.ascontiguousarray(res["ei"][1])
+        m = int(dst.max()) + 1 if Ep else 0
+        pos = np.full((N, k), -1, np.int64)
+        lib().sno_topk_weights(_p(res["s"]), _p(dst), Ep, m, k, float(thr), _p(np.empty(max(Ep, 1), np.float32)), _p(pos))
+        res["sel_pos"] = pos
     return res
 
 
