@@ -1065,6 +1065,35 @@ int sngnn_linkx_join_forward(const float *zA, const float *zX, const float *W, c
 int sngnn_linkx_join_backward(const float *grad_y, const float *y, const float *ax, const float *W, int64_t N, int H,
                               int lsm, float *g, float *grad_zA, float *grad_zX, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Jumping knowledge (models.py:810, 840, 869, 897): csrc/jk.hip.
+ * ------------------------------------------------------------------------ */
+/*
+ * Replaces: JumpingKnowledge('max') - torch.stack(xs, -1).max(-1)[0] over the L layers' rows - without the stacked
+ * [N, C, L] copy and the int64 index per element:
+ *   out[i] = max_l xs[l][i], which[i] = the layer it came from, as a scan in layer order: b = x_0, idx = 0, layer l
+ *   replaces b iff x_l > b || (isnan(x_l) && !isnan(b)).  These are torch's semantics exactly: the FIRST maximal layer
+ *   wins a tie, +0 and -0 tie (the first one's bits are returned), the first NaN wins and sticks.
+ *   xs      HOST array of L device pointers, each dev f32 [N, C] dense; read during the call (copied into the kernel's
+ *           arguments): nothing is allocated, nothing synchronises
+ *   out     dev f32 [N, C], must not alias an input (SNGNN_EINVAL)
+ *   which   dev u8 [N, C], or NULL when no gradient is wanted
+ * 1 <= L <= SNGNN_JK_MAX_LAYERS (SNGNN_ERANGE otherwise); C >= 1, N >= 0, no NULL row pointer (SNGNN_EINVAL);
+ * N == 0 is a no-op.  16-byte accesses where every pointer is 16-byte aligned, scalar ones otherwise.  Only enqueues.
+ */
+#define SNGNN_JK_MAX_LAYERS 8
+int sngnn_jk_max_forward(const float *const *xs, int L, int64_t N, int C, float *out, unsigned char *which, void *stream);
+/*
+ * Replaces: autograd of the same line - a scatter into a zeroed [N, C, L] tensor whose per-layer views are stride-L:
+ *   grads[l][i] = which[i] == l ? grad_out[i] : 0 for every layer with a non-NULL grads[l] (a NULL entry: that layer
+ *   wants no gradient).  Every element of every wanted layer is stored: no zero fill is needed before the call.
+ *   grads   HOST array of L device pointers (or NULL), each dev f32 [N, C] dense, distinct from grad_out and from each
+ *           other (SNGNN_EINVAL)
+ * Only enqueues.
+ */
+int sngnn_jk_max_backward(const float *grad_out, const unsigned char *which, int L, int64_t N, int C, float *const *grads,
+                          void *stream);
+
 /*
  * Measurement aid (no reference counterpart): while enabled, sngnn_agg_forward
  * records HIP events on the caller's stream around its launches;

@@ -116,6 +116,7 @@ SIGNATURES = {
     "sngnn_glognn_backward": (_i32, [_vp] * 6 + [_i32, _f64, _f64, _i32] + [_vp] * 5),
     "sngnn_linkx_join_supported": (_i32, [_i32]), "sngnn_linkx_join_forward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "sngnn_linkx_join_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_jk_max_forward": (_i32, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]), "sngnn_jk_max_backward": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "sngnn_profile_enable": (_i32, [_i32]),
     "sngnn_profile_last_forward": (_i32, [C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32), C.POINTER(_f32)]),
     "sngnn_gather_floor_workspace_bytes": (_i64, []), "sngnn_gather_floor": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp]),

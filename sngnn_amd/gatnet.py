@@ -7,7 +7,9 @@ The reference runs a layer as PyG's ``propagate``: gathers of the scores and of 
 scatter-max / exp / scatter-sum softmax and a weighted scatter-add.  Here the layer is ``ops.linear`` followed by
 ``ops.gat_propagate``; the device graph (original self loops dropped, one loop per node appended) comes from the shared
 ``GraphCache``.  Between layers ``bns[i]`` -> ``elu`` -> dropout run in torch (the reference's order; not the fused
-``ops.batch_norm_act``, whose order is another).  GPU tensors only (no CPU path)."""
+``ops.batch_norm_act``, whose order is another).  ``GATJK`` (models.py:846-900) is the same stack with every layer's
+rows joined by jumping knowledge (``jk.jk_max`` or ``torch.cat``) in front of ``final_project``.  GPU tensors only (no
+CPU path)."""
 from __future__ import annotations
 
 import math
@@ -17,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dist as sn_dist
-from . import ops
+from . import jk, ops
 from .graph import GLOBAL_CACHE, LOOPS_REPLACE
 
 
@@ -132,4 +134,53 @@ class GAT(nn.Module):
     def forward(self, data, adjs=None, x_batch=None):
         if adjs is not None or x_batch is not None:
             raise NotImplementedError("sampling=True (bipartite neighbour-sampled layers) is not implemented")
+        return F.log_softmax(self.forward_logits(data), dim=1)
+
+
+class GATJK(nn.Module):
+    """models.py:846-900 with ``jk_type`` 'max' or 'cat' (PyG's JumpingKnowledge has no parameters for either); 'lstm'
+    is not implemented.  Every layer is a concat ``GATConv`` of ``hidden_channels * heads`` columns, the last one
+    included; the jump takes every hidden layer's rows AFTER the elu and BEFORE the dropout, and the last layer's rows as
+    they are.  'max' is ``jk.jk_max`` (csrc/jk.hip), 'cat' ``torch.cat``."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers=2, dropout=0.5, heads=2, jk_type='max'):
+        super().__init__()
+        if jk_type not in ('max', 'cat'):
+            raise NotImplementedError(f"GATJK: jk_type {jk_type!r} is not implemented (only 'max' and 'cat')")
+        wide = hidden_channels * heads
+        self.convs = nn.ModuleList()
+        self.convs.append(GATConv(in_channels, hidden_channels, heads=heads, concat=True))
+        self.bns = nn.ModuleList()
+        self.bns.append(nn.BatchNorm1d(wide))
+        for _ in range(num_layers - 2):
+            self.convs.append(GATConv(wide, hidden_channels, heads=heads, concat=True))
+            self.bns.append(nn.BatchNorm1d(wide))
+        self.convs.append(GATConv(wide, hidden_channels, heads=heads))
+        self.dropout = dropout
+        self.activation = F.elu
+        self.jk_type = jk_type
+        self.final_project = nn.Linear(wide * num_layers if jk_type == 'cat' else wide, out_channels)
+
+    def reset_parameters(self):
+        for conv in self.convs:
+            conv.reset_parameters()
+        for bn in self.bns:
+            bn.reset_parameters()
+        self.final_project.reset_parameters()
+
+    def jump(self, xs):
+        return torch.cat(xs, dim=-1) if self.jk_type == 'cat' else jk.jk_max(xs)
+
+    def forward_logits(self, data):
+        """Everything before the final ``log_softmax`` (lets ``GraphedEpoch`` run the fused head kernel on it)."""
+        x, edge_index = data.x, data.edge_index
+        xs = []
+        for i, conv in enumerate(self.convs[:-1]):
+            x = self.activation(self.bns[i](conv(x, edge_index)))
+            xs.append(x)
+            x = F.dropout(x, p=self.dropout, training=self.training)
+        xs.append(self.convs[-1](x, edge_index))
+        return ops.linear(self.jump(xs), self.final_project)
+
+    def forward(self, data):
         return F.log_softmax(self.forward_logits(data), dim=1)

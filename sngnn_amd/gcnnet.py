@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import gcn, models, ops
+from . import gcn, jk, models, ops
 from .gcnii import _glorot, _norm_fusable
 from .gpr import _graph_of
 from .graph import Graph
@@ -202,7 +202,7 @@ class GCNJK(_HiddenStack):
     def jump(self, xs):
         if self.jk_type == 'cat':
             return torch.cat(xs, dim=-1)
-        return torch.stack(xs, dim=-1).max(dim=-1)[0]
+        return jk.jk_max(xs)          # torch.stack(xs, -1).max(-1)[0], exactly (csrc/jk.hip)
 
     def forward_logits(self, data):
         x, edge_index = data.x, data.edge_index
