@@ -319,7 +319,11 @@ int sngnn_agg_forward_rows(const sngnn_graph_t *g, const float *n, const float *
  * candidates, no head epilogue), else in a launch of its own; 0 = always a launch of its own; v > 1 = inside the
  * main launch on v workgroups.  Same selections and kept weights either way; the rows' sums agree bit for bit for
  * rows of at most 128 candidates and to rounding (another summation order) for the bigger ones;
- * knob 10 = copies of sngnn_cosine_hist's counter table in LDS (see there). */
+ * knob 10 = copies of sngnn_cosine_hist's counter table in LDS (see there);
+ * knob 11 = how the forward's work-item roles address what they gather (table rows, norms, column ids, filter rows):
+ * 0 (default) = through buffer resources with 32-bit offsets when the fp32 table has fewer than 2^31 bytes (slots and
+ * lanes nobody reads get an out-of-range offset: zeros, no request), the flat form otherwise; 1 = the flat form
+ * (64-bit pointers) always.  The same bits either way - the A/B of a measurement, and the path of bigger tables. */
 int sngnn_tuning_set(int which, int value);
 /* how many workgroups of the last sngnn_agg_forward* launch on this process finalized split rows (0 = the
  * finalize was a launch of its own, or there was nothing to finalize) - measurement aid, see knob 9 */

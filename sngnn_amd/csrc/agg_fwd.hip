@@ -78,6 +78,9 @@ static int g_table_mode = 0;
 // (sngnn_tuning_set(8, d): wave rows with fewer than d in-edges skip the fp16 filter; -1 = the library's rule)
 static int g_filt_min_deg = -1;
 int sngnn::g_fin_inline = 1;
+// sngnn_tuning_set(11, v): how the work-item roles address their gathers - 0 = buffer resources where the table allows
+// (fwd_plan.h: fwd_buffer_form), 1 = the flat form always
+static int g_addr_mode = 0;
 int sngnn::g_last_fin_blocks = 0;
 extern "C" int sngnn_last_forward_finalize_workgroups(void) { return sngnn::g_last_fin_blocks; }
 // a value no earlier call of this process has used (the finalize role: the tasks' done words)
@@ -89,7 +92,8 @@ unsigned long long sngnn::next_fin_nonce()
 bool sngnn::fwd_scores_on_the_fly_forced() { return g_table_mode == 2; }
 extern "C" int sngnn_tuning_set(int which, int value)
 {
-    SN_REQUIRE(which == 0 || (which >= 2 && which <= 10), SNGNN_EINVAL, "unknown tuning knob");
+    SN_REQUIRE(which == 0 || (which >= 2 && which <= 11), SNGNN_EINVAL, "unknown tuning knob");
+    if (which == 11) { g_addr_mode = value == 1 ? 1 : 0; return SNGNN_OK; }
     if (which == 10) return sngnn::set_hist_copies(value);
     if (which == 9) { sngnn::g_fin_inline = value < 0 ? 0 : value; return SNGNN_OK; }
     if (which == 8) { g_filt_min_deg = value; return SNGNN_OK; }
@@ -212,6 +216,10 @@ static int launch_forward(const FwdCall &c, const RowCfg &cfg, const float *n, c
 
     FwdArgs a;
     a.n = n; a.nrm = nrm; a.C = C; a.N = (int)g->N; a.row_off = (int)g->row_off;
+    // fp32 tables below 2 GiB are read through buffer resources (agg_fwd_src.h); the half path keeps the flat form
+    const int64_t table_bytes = g->Ntot * (int64_t)C * (c.dtype == 0 ? 4 : 2);
+    const bool buf = c.dtype == 0 && fwd_buffer_form(table_bytes, std::max<int64_t>(4 * g->Ep, 16 * g->N), g_addr_mode);
+    a.Ntot = (int)g->Ntot; a.n_bytes = buf ? (unsigned)table_bytes : 0u;
     a.filt = nrm ? (const uint4 *)filt : nullptr;
     // (sngnn_filter_enable(2) forces it at any threshold: the tests' and the fuzz runs' way in)
     // (top_k >= 4: at top_k 1 the small-row form gains 1.5 us where it prunes - 39.3 -> 37.6-38.8 us at thr
@@ -300,12 +308,16 @@ static int launch_forward(const FwdCall &c, const RowCfg &cfg, const float *n, c
         SN_REQUIRE(g->n_split == 0 || a.use_cand, SNGNN_EINVAL,
                    "no head epilogue: this graph's biggest row takes the scratch-score finalize (sngnn_agg_head_supported)");
         // (the plain kernels: the head rides in the second launch)
-        return launch_agg_fwd_vec<float, 4>(cfg, a, max_split, ev, st);
+        return buf ? launch_agg_fwd_buf_vec<4>(cfg, a, max_split, ev, st)
+                   : launch_agg_fwd_vec<float, 4>(cfg, a, max_split, ev, st);
     }
     if (a.epi_flags != 0) {
         SN_REQUIRE(cfg.vec == 4, SNGNN_EINVAL, "the store epilogue needs C % 4 == 0 (16-byte rows)");
-        return launch_agg_fwd_epi_v4(cfg, a, max_split, ev, st);
+        return buf ? launch_agg_fwd_epi_buf_v4(cfg, a, max_split, ev, st)
+                   : launch_agg_fwd_epi_v4(cfg, a, max_split, ev, st);
     }
+    if (buf)
+        return dispatch_vec(cfg, [&](auto vec) { return launch_agg_fwd_buf_vec<decltype(vec)::value>(cfg, a, max_split, ev, st); });
     // (the half path: n = the raw half rows, nrm == NULL, no epilogue / head / kept bits)
     return SNGNN_LAUNCH_VEC(launch_agg_fwd_vec, cfg, c.dtype, a, max_split, ev, st);
 }

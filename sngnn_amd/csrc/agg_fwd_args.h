@@ -58,6 +58,11 @@ struct FwdArgs {
     // the kernels' template parameter S; rows<S>() / outs<S>() / out_at<S>() below.  Everything else stays fp32.)
     const float *n;
     const float *nrm;
+    // the table's size: Ntot rows, n_bytes = Ntot * C * (bytes per value) - what the buffer form of the work-item
+    // roles builds its resources from (agg_fwd_src.h; n_bytes == 0: the table has 2 GiB or more and the call runs the
+    // flat form, fwd_plan.h: fwd_buffer_form)
+    int Ntot;
+    unsigned n_bytes;
     float delta;          // OTF: bound on |fast - exact| (launcher: (4 C + 32) 2^-24)
     const uint4 *filt;    // [Ntot, filter_row_halfs(C)] fp16 filter rows (agg_fwd_filter.h) or nullptr
     int filt_small;       // the filter also in front of the SMALL rows (small_rows_set_filt): pays when a threshold
@@ -188,12 +193,18 @@ unsigned long long next_fin_nonce();
 // Defined one per translation unit: storage type S (float, __half, __hip_bfloat16: agg_fwd[_f16|_bf16]_v*.hip) x VEC
 // values per lane (entry.h: SNGNN_LAUNCH_VEC).  The unit-row passes and the store epilogue exist for fp32 rows only,
 // the filter pass and the epilogue for 16-byte rows only (agg_fwd_v4.hip, agg_fwd_v4e.hip).
+// fp32 rows have the forward in two forms (agg_fwd_src.h): launch_agg_fwd_buf_vec / launch_agg_fwd_epi_buf_v4 read
+// through buffer resources (agg_fwd_v*.hip, agg_fwd_v4e.hip), launch_agg_fwd_vec<float, ..> / launch_agg_fwd_epi_v4
+// are the flat form (agg_fwd_flat_v*.hip, agg_fwd_flat_v4e.hip); the caller picks by fwd_plan.h: fwd_buffer_form.
 template <typename S, int VEC>
 int launch_agg_fwd_vec(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
 template <typename S, int VEC>
 int launch_normalize_vec(const RowCfg &cfg, const float *h, int64_t rows, int C, float *n, float *nrm, void *filt,
                          hipStream_t st);
 int launch_agg_fwd_epi_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+template <int VEC>
+int launch_agg_fwd_buf_vec(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
+int launch_agg_fwd_epi_buf_v4(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st);
 int launch_filter_v4(const RowCfg &cfg, const float *n, int64_t rows, int C, void *filt, hipStream_t st);
 
 }  // namespace sngnn

@@ -61,9 +61,10 @@ __device__ __forceinline__ float fdot8(const uint4 &a, const uint4 &b)
 // sc[t - e0] = s~, ids[t - e0] = source id.  GF lanes x 16 bytes = one filter row; the wave's
 // 64 / GF groups stride over the edges, UF rows in flight per group, column ids one
 // iteration ahead (as in score_edges).
-template <int GF>
-__device__ __forceinline__ void filter_scores(const uint4 *__restrict__ filt, const int32_t *__restrict__ col,
-                                              int self, int rs, int e0, int e1, float *sc, int *ids)
+// src: how the filter rows and column ids are read (agg_fwd_src.h: flat, or buffer-addressed - then a slot beyond e1
+// gets an out-of-range offset instead of the row's own filter row)
+template <int GF, typename SRC>
+__device__ __forceinline__ void filter_scores(const SRC &src, int self, int rs, int e0, int e1, float *sc, int *ids)
 {
     constexpr int NGF = 64 / GF;
 #ifndef SNGNN_FILT_UF
@@ -72,12 +73,12 @@ __device__ __forceinline__ void filter_scores(const uint4 *__restrict__ filt, co
     constexpr int UF = GF >= 32 ? 2 : (GF == 16 ? 4 : SNGNN_FILT_UF);
     const int lane = lane_id();
     const int gid = lane / GF, lf = lane % GF;
-    const uint4 fi = filt[(size_t)self * GF + lf];
+    const uint4 fi = src.template filt<uint4>(self, GF, lf);
     int jn[UF];
 #pragma unroll
     for (int u = 0; u < UF; ++u) {
         const int t = e0 + u * NGF + gid;
-        jn[u] = t < e1 ? col[rs + t] : self;
+        jn[u] = src.col_if(rs + t, t < e1, self);
     }
     for (int base = e0; base < e1; base += NGF * UF) {
         int t[UF], j[UF];
@@ -88,11 +89,11 @@ __device__ __forceinline__ void filter_scores(const uint4 *__restrict__ filt, co
             j[u] = jn[u];
         }
 #pragma unroll
-        for (int u = 0; u < UF; ++u) x[u] = filt[(size_t)j[u] * GF + lf];
+        for (int u = 0; u < UF; ++u) x[u] = src.template filt_if<uint4>(j[u], t[u] < e1, GF, lf);
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
             const int tn = t[u] + NGF * UF;
-            jn[u] = tn < e1 ? col[rs + tn] : self;
+            jn[u] = src.col_if(rs + tn, tn < e1, self);
         }
 #pragma unroll
         for (int u = 0; u < UF; ++u) {

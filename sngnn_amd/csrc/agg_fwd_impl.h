@@ -3,6 +3,7 @@
 //   agg_fwd_args.h    FwdArgs and its store epilogue; what the forward computes (the opening comment)
 //   agg_fwd_head.h    the classification head's role
 //   agg_fwd_select.h  scoring and top-k primitives
+//   agg_fwd_src.h     how the work-item roles read what they gather: flat pointers, or buffer resources
 //   agg_fwd_fin.h     the five forms of the split rows' finalize
 //   agg_fwd_roles.h   the unit-row and filter passes, the three work-item roles, k_agg_fwd
 // and every launch decision in fwd_plan.h (plain C++): the launchers below fill its input from FwdArgs, call it
@@ -117,9 +118,10 @@ int launch_split_finalize(const FwdArgs &a, const FwdPlan &p, hipStream_t st)
     return SNGNN_OK;
 }
 
-template <int VEC, int G, int R, int EPI, typename S = float>
+template <int VEC, int G, int R, int EPI, typename S = float, bool BUF = false>
 int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hipStream_t st)
 {
+    static_assert(!BUF || std::is_same<S, float>::value, "buffer-addressed reads: fp32 tables");
     constexpr bool F32 = std::is_same<S, float>::value;        // (half rows: on the fly only, launcher's check)
     const int reps = ev ? std::max(g_prof_reps, 1) : 1;
     const FwdPlan p = fwd_plan(fwd_plan_input<G, S>(a0, max_split_deg));
@@ -133,8 +135,8 @@ int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hi
     if (ev) SN_HIP(hipEventRecord(ev[0], st));
 #define SNGNN_FWD_LAUNCH(FILTV, OTFV, FSV)                                                              \
     do {                                                                                              \
-        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true, S><<<grid, BLOCK, 0, st>>>(a); \
-        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false, S><<<grid, BLOCK, 0, st>>>(a);           \
+        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true, S, BUF><<<grid, BLOCK, 0, st>>>(a); \
+        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false, S, BUF><<<grid, BLOCK, 0, st>>>(a);           \
     } while (0)
     for (int rep = 0; rep < reps && grid > 0; ++rep) {
         if (!F32 || a.nrm == nullptr) {                          // OTF: a.n holds the raw rows
@@ -175,6 +177,17 @@ int launch_agg_fwd_epi(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipS
 {
     return launch_agg_fwd_impl<VEC, G, R, 1>(a, max_split_deg, ev, st);
 }
+// the same two with the work-item roles in their buffer form (fp32 tables; fwd_plan.h: fwd_buffer_form)
+template <int VEC, int G, int R>
+int launch_agg_fwd_buf(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
+{
+    return launch_agg_fwd_impl<VEC, G, R, 0, float, true>(a, max_split_deg, ev, st);
+}
+template <int VEC, int G, int R>
+int launch_agg_fwd_epi_buf(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipStream_t st)
+{
+    return launch_agg_fwd_impl<VEC, G, R, 1, float, true>(a, max_split_deg, ev, st);
+}
 
 }  // namespace sngnn
 
@@ -184,5 +197,13 @@ int launch_agg_fwd_epi(const FwdArgs &a, int max_split_deg, hipEvent_t *ev, hipS
                                           hipStream_t st)                                                              \
     {                                                                                                                  \
         SNGNN_DISPATCH_GRS(launch_agg_fwd, VEC, S, cfg, a, max_split_deg, ev, st)                                      \
+    }
+// the buffer form of the fp32 forward at VEC values per lane
+#define SNGNN_AGG_FWD_BUF_TU(VEC)                                                                                      \
+    template <>                                                                                                        \
+    int sngnn::launch_agg_fwd_buf_vec<VEC>(const RowCfg &cfg, const FwdArgs &a, int max_split_deg, hipEvent_t *ev,     \
+                                           hipStream_t st)                                                             \
+    {                                                                                                                  \
+        SNGNN_DISPATCH_GR(launch_agg_fwd_buf, VEC, cfg, a, max_split_deg, ev, st)                                      \
     }
 

@@ -1,12 +1,14 @@
 // The passes in front of the main kernel (unit rows, fp16 filter rows), the three work-item roles of the main kernel
 // - small-row sets, wave rows, split-row tasks - with the scoring passes they share, and the kernel itself
 // (k_agg_fwd), whose last workgroups may run the in-launch finalize.  Needs agg_fwd_args.h, agg_fwd_select.h,
-// agg_fwd_filter.h (filter_scores, approx_candidates), agg_fwd_fin.h and fwd_plan.h (FWD_WAVES_PER_SIMD).
+// agg_fwd_src.h (FwdSrc: every role reads its gathered inputs through one, `src`), agg_fwd_filter.h (filter_scores,
+// approx_candidates), agg_fwd_fin.h and fwd_plan.h (FWD_WAVES_PER_SIMD).
 #pragma once
 #include "agg_fwd_args.h"
 #include "agg_fwd_filter.h"
 #include "agg_fwd_fin.h"
 #include "agg_fwd_select.h"
+#include "agg_fwd_src.h"
 #include "fwd_plan.h"
 
 namespace sngnn {
@@ -85,8 +87,12 @@ __global__ __launch_bounds__(BLOCK) void k_filter_rows(const float *__restrict__
 // ---------------------------------------------------------------------------
 // One set of 64/G small rows (one per lane group) whose column ids are already in
 // LDS (s_col[gid][t]).  d = this group's row descriptor (deg 0 for a padding slot).
-template <int VEC, int G, int R, bool OTF, int EPI, typename S = float>
-__device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, bool valid,
+// src: how the gathered inputs are read (agg_fwd_src.h).  The buffer form gives a slot beyond the row's edges an
+// out-of-range offset instead of `self`, and skips a slot beyond EVERY row of the set altogether (t0 + u >= dmax is
+// wave-uniform: a scalar branch around the load and the dot) - the sets are dealt by four-degree buckets, so on an
+// arxiv-like graph, where most rows have one or two in-edges, that is half the slots.
+template <int VEC, int G, int R, bool OTF, int EPI, typename S, typename SRC>
+__device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src, const int4 d, bool valid,
                                                int *lds_wave, const int *s_col_set)
 {
     using RowT = Row<VEC, G, R>;
@@ -105,8 +111,9 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
     float *s_w = reinterpret_cast<float *>(lds_wave + 3 * SETW) + gid * SMALL_T;
 
     RowT ni;
-    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
-    const int dmax = wave_max_i(deg);
+    src.row(ni, self);
+    // (the form that skips slots takes the maximum into a scalar register: the skip is a scalar branch)
+    const int dmax = SRC::skips_dead ? __builtin_amdgcn_readfirstlane(wave_max_i(deg)) : wave_max_i(deg);
     float inv_i = 0.f, q_i = 0.f;
     if constexpr (OTF) {
         q_i = group_sum<G>(ni.dot_partial(ni));
@@ -116,18 +123,21 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
     RowT acc;
     acc.zero();
     unsigned kb = 0u;                 // the row's kept bits (a.kbits)
-    for (int t0 = 0; t0 < dmax; t0 += U) {
-        RowT x[U];
-        float nj[U];
+    // one step: NU slots, t0 .. t0 + NU - 1, of every row of the set - their loads first, all in flight together
+    auto step = [&](int t0, auto nu_c) __attribute__((always_inline)) {
+        constexpr int NU = decltype(nu_c)::value;
+        RowT x[NU];
+        float nj[NU];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = (t0 + u) < deg ? s_col[t0 + u] : self;
-            x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
+        for (int u = 0; u < NU; ++u) {
+            const bool live = (t0 + u) < deg;
+            const int j = src.pick(live, s_col[t0 + u], self);
+            src.row_if(x[u], j, live);
             if constexpr (OTF) nj[u] = 1.f;
-            else nj[u] = rank ? 0.f : a.nrm[j];   // a streaming row weighs the row it has just scored
+            else nj[u] = src.nrm_unless(j, live, rank);   // a streaming row weighs the row it has just scored
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
+        for (int u = 0; u < NU; ++u) {
             float s;
             if constexpr (OTF) {
                 s = edge_score<VEC, G, R>(ni, inv_i, x[u]);
@@ -154,10 +164,26 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
                 }
             }
         }
+    };
+    for (int t0 = 0; t0 < dmax; t0 += U) {
+        // (the form that skips slots: a step of as many slots as the set's longest row still has - wave-uniform, a
+        // scalar branch to a step without the others' loads and dots; every step is branch-free inside)
+        // (Not a branch around each slot's load and dot inside one step: the compiler then keeps every slot's
+        // column-id read, its wait and its load behind the slot's own branch - four LDS round trips in a row in front
+        // of four loads that are meant to be in flight together.  Copies of the step cost code, not time.)
+        const int nu = SRC::skips_dead ? min(dmax - t0, U) : U;
+        if (nu == U) step(t0, std::integral_constant<int, U>{});
+        else if constexpr (SRC::skips_dead && U > 1) {
+            if (nu == 1) step(t0, std::integral_constant<int, 1>{});
+            else if constexpr (U > 2) {                           // U == 4
+                if (nu == 2) step(t0, std::integral_constant<int, 2>{});
+                else step(t0, std::integral_constant<int, 3>{});
+            }
+        }
     }
     if (a.inv_norm && valid && lg == 0) {
         if constexpr (OTF) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
-        else a.inv_norm[i] = ieee_div(1.0f, a.nrm[self]);
+        else a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
 
     if constexpr (OTF) {
@@ -187,7 +213,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
                 for (int t = 0; t < dm; ++t) {
                     const bool live = row_amb && t < deg;
                     RowT xr;
-                    xr.load(a.rows<S>() + (size_t)(live ? s_col[t] : self) * a.C, a.C, lg);
+                    src.row_if(xr, src.pick(live, s_col[t], self), live);
                     const float se = exact_score_raw<VEC, G, R>(nu, xr);
                     if (live && lg == 0) s_sc[t] = se;
                 }
@@ -225,9 +251,9 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
                 if (w != SNGNN_UNSELECTED) {
                     const int j = s_col[t];
                     RowT xr;
-                    xr.load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
+                    src.row(xr, j);
                     if constexpr (OTF) acc.axpy(w, xr);
-                    else acc.axpy(w * a.nrm[j], xr);
+                    else acc.axpy(w * src.nrm(j), xr);
                 }
             }
         }
@@ -251,8 +277,8 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const int4 d, b
 // are fetched and scored in fp32: every edge of the exact selection is a candidate (the filter header's
 // argument), the exact rule then runs on the candidates' exact scores, so indices, weights, ranks and kept
 // bits are those of the unfiltered set, bit for bit.
-template <int VEC, int G, int R, int EPI>
-__device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4 d, bool valid,
+template <int VEC, int G, int R, int EPI, typename SRC>
+__device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const SRC &src, const int4 d, bool valid,
                                                     int *lds_wave, const int *s_col_set)
 {
     static_assert(G >= SMALL_T, "one lane per edge of a small row");
@@ -268,7 +294,6 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
     const bool rank = deg > a.k;                         // (a.k >= 0: the filter belongs to selecting calls)
     const bool need_sc = rank || emit;
     const int self = i + a.row_off;
-    const uint2 *f2 = reinterpret_cast<const uint2 *>(a.filt);
 
     const int *s_col = s_col_set + gid * SMALL_T;
     float *s_sc = reinterpret_cast<float *>(lds_wave + 2 * SETW) + gid * SMALL_T;   // approximate, then exact scores
@@ -277,7 +302,7 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
 
     uint2 fi[R];
 #pragma unroll
-    for (int q = 0; q < R; ++q) fi[q] = f2[(size_t)self * FR + q * G + lg];
+    for (int q = 0; q < R; ++q) fi[q] = src.template filt<uint2>(self, FR, q * G + lg);
     const int dmax = wave_max_i(deg);
 
     // phase 1: approximate scores of all edges from the filter rows
@@ -285,9 +310,10 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
         uint2 x[UF][R];
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
-            const int j = (t0 + u) < deg ? s_col[t0 + u] : self;
+            const bool live = (t0 + u) < deg;
+            const int j = src.pick(live, s_col[t0 + u], self);
 #pragma unroll
-            for (int q = 0; q < R; ++q) x[u][q] = f2[(size_t)j * FR + q * G + lg];
+            for (int q = 0; q < R; ++q) x[u][q] = src.template filt_if<uint2>(j, live, FR, q * G + lg);
         }
 #pragma unroll
         for (int u = 0; u < UF; ++u) {
@@ -334,7 +360,7 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
     // (the row's own fp32 unit row only now, with the first candidates' rows: a set without candidates - most
     // sets behind a threshold that prunes - touches one-line filter rows only)
     RowT ni;
-    if (ncmax > 0) ni.load(a.n + (size_t)self * a.C, a.C, lg);
+    if (ncmax > 0) src.row(ni, self);
     else ni.zero();
     for (int q0 = 0; q0 < ncmax; q0 += U) {
         RowT x[U];
@@ -343,9 +369,10 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             e[u] = (q0 + u) < nc ? s_c[q0 + u] : -1;
-            const int j = e[u] >= 0 ? s_col[e[u]] : self;
-            x[u].load(a.n + (size_t)j * a.C, a.C, lg);
-            nj[u] = need_sc ? 0.f : a.nrm[j];                 // a streaming row weighs the row it has just scored
+            const bool live = e[u] >= 0;
+            const int j = src.pick(live, s_col[live ? e[u] : 0], self);
+            src.row_if(x[u], j, live);
+            nj[u] = src.nrm_unless(j, live, need_sc);         // a streaming row weighs the row it has just scored
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -362,7 +389,7 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
             }
         }
     }
-    if (a.inv_norm && valid && lg == 0) a.inv_norm[i] = ieee_div(1.0f, a.nrm[self]);
+    if (a.inv_norm && valid && lg == 0) a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
 
     if (need_sc) {
         wave_lds_sync();
@@ -390,8 +417,8 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
             if (w != SNGNN_UNSELECTED) {
                 const int j = s_col[t];
                 RowT xr;
-                xr.load(a.n + (size_t)j * a.C, a.C, lg);
-                acc.axpy(w * a.nrm[j], xr);
+                src.row(xr, j);
+                acc.axpy(w * src.nrm(j), xr);
             }
         }
         wave_lds_sync();       // s_sc / s_w are reused by the next set
@@ -410,8 +437,8 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const int4
 // current one, so a set costs one memory round trip (its feature rows) instead of a
 // chain of three (descriptor -> columns -> rows).
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool OTF, int EPI, bool FS = false, typename S = float>
-__device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int stride, int nsets, int *lds_wave)
+template <int VEC, int G, int R, bool OTF, int EPI, bool FS, typename S, typename SRC>
+__device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int set0, int stride, int nsets, int *lds_wave)
 {
     constexpr int RPW = 64 / G;
     constexpr int CPL = (RPW * SMALL_T + 63) / 64;      // column ids per lane per set
@@ -421,7 +448,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
 
     auto load_desc = [&](int st) -> int4 {
         const int slot = a.n_med_end + st * RPW + gid;
-        int4 d = (st < nsets && slot < a.N) ? a.rdesc[slot] : make_int4(0, 0, 0, -1);
+        int4 d = src.desc_if(slot, st < nsets && slot < a.N);
         if (a.row_flag != nullptr && d.w >= 0 && a.skip_row(d.x)) d = make_int4(0, 0, 0, -1);   // not this pass's row
         return d;
     };
@@ -433,7 +460,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
             const int r = q / SMALL_T, t = q % SMALL_T;
             // descriptor of row r of the set lives in the lanes of group r
             const int rss = __shfl(d.w, r * G, 64), dg = __shfl(d.z, r * G, 64);
-            c[m] = (r < RPW && t < dg) ? a.col_s[rss + t] : 0;      // consecutive slots: one stream
+            c[m] = src.col_s_if(rss + t, r < RPW && t < dg);        // consecutive slots: one stream
         }
     };
     auto store_cols = [&](const int (&c)[CPL], int *dst) {
@@ -466,11 +493,11 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
             bool done = false;
             if constexpr (FS && G >= SMALL_T && !OTF) {
                 if (a.filt_small) {                               // (uniform)
-                    small_rows_set_filt<VEC, G, R, EPI>(a, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
+                    small_rows_set_filt<VEC, G, R, EPI>(a, src, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
                     done = true;
                 }
             }
-            if (!done) small_rows_set<VEC, G, R, OTF, EPI, S>(a, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
+            if (!done) small_rows_set<VEC, G, R, OTF, EPI, S>(a, src, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
         }
         store_cols(cols, lds_wave + SETW * (buf ^ 1));
         d_cur = d_nxt;
@@ -495,8 +522,8 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, int set0, int strid
 //           except: a streaming edge within delta of thr is scored exactly; with exact_all EVERY
 //           edge is (the paths that rank from scores in HBM scratch: top_k > CAND_MAX_K, hubs
 //           beyond the candidate finalize, ranks of a streaming split row).
-template <int VEC, int G, int R, bool OTF, typename S = float>
-__device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, int e0, int e1,
+template <int VEC, int G, int R, bool OTF, typename S, typename SRC>
+__device__ __forceinline__ void score_edges(const FwdArgs &a, const SRC &src, int self, int rs, int e0, int e1,
                                             const Row<VEC, G, R> &ni, float inv_i, bool stream,
                                             float *sc, int sc_off, Row<VEC, G, R> &acc,
                                             int *ids_lds = nullptr, bool exact_all = false)
@@ -516,7 +543,7 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int t = e0 + u * NG + gid;
-        jn[u] = t < e1 ? a.col[rs + t] : self;
+        jn[u] = src.col_if(rs + t, t < e1, self);
     }
     for (int base = e0; base < e1; base += NG * U) {
         int t[U], j[U];
@@ -531,14 +558,14 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, 
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            x[u].load(a.rows<S>() + (size_t)j[u] * a.C, a.C, lg);
+            src.row_if(x[u], j[u], act[u]);
             if constexpr (OTF) nj[u] = 1.f;
-            else nj[u] = stream ? a.nrm[j[u]] : 0.f;
+            else nj[u] = stream ? src.nrm_if(j[u], act[u]) : 0.f;       // (stream: wave-uniform)
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int tn = t[u] + NG * U;
-            jn[u] = tn < e1 ? a.col[rs + tn] : self;
+            jn[u] = src.col_if(rs + tn, tn < e1, self);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -578,8 +605,8 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, int self, int rs, 
 // sc[idx] = <n_i, n_j>.  U rows per lane group in flight; a slot past the end repeats the
 // last listed edge and stores nothing.
 // (OTF: ni is the UNIT target row, the listed rows are raw and are normalised in registers)
-template <int VEC, int G, int R, bool OTF, typename S = float>
-__device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R> &ni, const int *list, int ncand,
+template <int VEC, int G, int R, bool OTF, typename S, typename SRC>
+__device__ __forceinline__ void score_list(const SRC &src, const Row<VEC, G, R> &ni, const int *list, int ncand,
                                            const int *ids, float *sc)
 {
     using RowT = Row<VEC, G, R>;
@@ -597,7 +624,7 @@ __device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R
         for (int u = 0; u < U; ++u) {
             const int q = q0 + u * NG + gid;
             idx[u] = list[min(q, ncand - 1)];
-            x[u].load(a.rows<S>() + (size_t)ids[idx[u]] * a.C, a.C, lg);
+            src.row(x[u], ids[idx[u]]);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -626,8 +653,8 @@ __device__ __forceinline__ void score_list(const FwdArgs &a, const Row<VEC, G, R
 //         ones).  Only a row that fails this test - ties and near ties at the cut - takes the
 //         candidate path.  (Not for split-row tasks: their keys are merged with other tasks'
 //         keys by the finalize, which needs them exact; not when ranks are emitted.)
-template <int VEC, int G, int R, bool OTF, typename S = float>
-__device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC, G, R> &ni, float inv_i, int self,
+template <int VEC, int G, int R, bool OTF, typename S, typename SRC>
+__device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const SRC &src, const Row<VEC, G, R> &ni, float inv_i, int self,
                                                  int rs, int e0, int e1, float *sc, int *list, int *ids, int lowbits,
                                                  bool optimistic = false)
 {
@@ -638,11 +665,11 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
     if constexpr (OTF) {
         RowT unused;
         unused.zero();
-        score_edges<VEC, G, R, true, S>(a, self, rs, e0, e1, ni, inv_i, false, sc, e0, unused, ids);
+        score_edges<VEC, G, R, true, S>(a, src, self, rs, e0, e1, ni, inv_i, false, sc, e0, unused, ids);
         eps = a.delta;
     } else {
         constexpr int GF = G * R / 2;                // 16-byte lanes per filter row (VEC == 4)
-        filter_scores<GF>(a.filt, a.col, self, rs, e0, e1, sc, ids);
+        filter_scores<GF>(src, self, rs, e0, e1, sc, ids);
         eps = FILT_EPS;
     }
     wave_lds_sync();
@@ -678,9 +705,9 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
         if constexpr (OTF) {
             RowT nu = ni;
             normalize_in_place<VEC, G, R>(nu);
-            score_list<VEC, G, R, true, S>(a, nu, list, ncand, ids, sc);
+            score_list<VEC, G, R, true, S>(src, nu, list, ncand, ids, sc);
         } else {
-            score_list<VEC, G, R, false>(a, ni, list, ncand, ids, sc);
+            score_list<VEC, G, R, false, S>(src, ni, list, ncand, ids, sc);
         }
     }
     wave_lds_sync();
@@ -695,8 +722,8 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const Row<VEC
 // ---------------------------------------------------------------------------
 // Class B: SMALL_T < deg <= WAVE_T, one wave per row.
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool FILT, bool OTF, int EPI, typename S = float>
-__device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_wave)
+template <int VEC, int G, int R, bool FILT, bool OTF, int EPI, typename S, typename SRC>
+__device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int item, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
     constexpr int NG = 64 / G;
@@ -716,7 +743,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     int *s_ids = lds_wave + 2 * WAVE_T;                      // [WAVE_T]
 
     RowT ni;
-    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
+    src.row(ni, self);
     float inv_i = 0.f, q_i = 0.f;
     if constexpr (OTF) {
         q_i = group_sum<G>(ni.dot_partial(ni));
@@ -729,14 +756,14 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     // asked for on a streaming row included: their order needs exact scores too)
     const bool banded = OTF ? need_sc : (FILT && rank && deg >= a.filt_min_deg);
     if (!banded)
-        score_edges<VEC, G, R, OTF, S>(a, self, rs, 0, deg, ni, inv_i, !rank, need_sc ? s_sc : nullptr, 0, acc,
+        score_edges<VEC, G, R, OTF, S>(a, src, self, rs, 0, deg, ni, inv_i, !rank, need_sc ? s_sc : nullptr, 0, acc,
                                     rank ? s_ids : nullptr);
 
     if (need_sc) {
         WaveSel ws;
         if constexpr (FILT || OTF) {
             if (banded) {
-                ws = banded_select<VEC, G, R, OTF, S>(a, ni, inv_i, self, rs, 0, deg, s_sc, s_list, s_ids, 7,
+                ws = banded_select<VEC, G, R, OTF, S>(a, src, ni, inv_i, self, rs, 0, deg, s_sc, s_list, s_ids, 7,
                                                    /*optimistic=*/OTF && !emit);
             } else {
                 wave_lds_sync();
@@ -787,9 +814,9 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
                     const int idx = s_list[min(q, nsel - 1)];
                     const int j = s_ids[idx];
                     w[u] = q < nsel ? s_sc[idx] : 0.f;
-                    x[u].load(a.rows<S>() + (size_t)j * a.C, a.C, lg);
+                    src.row(x[u], j);
                     if constexpr (OTF) nj[u] = 1.f;
-                    else nj[u] = a.nrm[j];
+                    else nj[u] = src.nrm(j);
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) acc.axpy(w[u] * nj[u], x[u]);
@@ -806,7 +833,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
     // column-id loads behind it - the pointers are not restrict)
     if (lane == 0 && a.inv_norm) {
         if constexpr (OTF) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
-        else a.inv_norm[i] = ieee_div(1.0f, a.nrm[self]);
+        else a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
     wave_lds_sync();            // the wave's LDS scratch is reused by its next item
 }
@@ -817,8 +844,8 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, int item, int *lds_w
 // FIN: the row's finalize runs in THIS launch (fin_block_pair / fin_group_batch / fin_stream_row) - what it reads
 // or overwrites is stored at agent scope, then the task says "done".  The launches whose finalize is the next
 // launch run the FIN = false instantiation: plain stores, the code of round 4.
-template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN, typename S = float>
-__device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wave)
+template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN, typename S, typename SRC>
+__device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int tq, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
     const int lane = lane_id();
@@ -834,14 +861,14 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wav
     const bool cand = rank && a.use_cand;        // chunk-local top-k -> candidates
 
     RowT ni;
-    ni.load(a.rows<S>() + (size_t)self * a.C, a.C, lg);
+    src.row(ni, self);
     float inv_i = 0.f;
     if constexpr (OTF) {
         const float q_i = group_sum<G>(ni.dot_partial(ni));
         inv_i = inv_norm_of(q_i);
         if (c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
     } else {
-        if (c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, a.nrm[self]);
+        if (c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
 
     RowT acc;
@@ -849,14 +876,14 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wav
     float *s_sc = reinterpret_cast<float *>(lds_wave);          // [CHUNK], chunk-local
     float *sc_glb = (!cand && (rank || emit)) ? a.scores + a.split_soff[p] : nullptr;   // HBM scratch
     if ((FILT || OTF) && cand) { /* scored below, in two precisions */ }
-    else if (cand) score_edges<VEC, G, R, OTF, S>(a, self, rs, e0, e1, ni, inv_i, !rank, s_sc, e0, acc);   // LDS
+    else if (cand) score_edges<VEC, G, R, OTF, S>(a, src, self, rs, e0, e1, ni, inv_i, !rank, s_sc, e0, acc);   // LDS
     // HBM scratch (ranked later from those scores: OTF writes exact ones) / none (pure streaming)
-    else score_edges<VEC, G, R, OTF, S>(a, self, rs, e0, e1, ni, inv_i, !rank, sc_glb, 0, acc, nullptr,
+    else score_edges<VEC, G, R, OTF, S>(a, src, self, rs, e0, e1, ni, inv_i, !rank, sc_glb, 0, acc, nullptr,
                                      /*exact_all=*/sc_glb != nullptr);
     if (cand) {
         WaveSel ws;
         if constexpr (FILT || OTF) {
-            ws = banded_select<VEC, G, R, OTF, S>(a, ni, inv_i, self, rs, e0, e1, s_sc, lds_wave + CHUNK,
+            ws = banded_select<VEC, G, R, OTF, S>(a, src, ni, inv_i, self, rs, e0, e1, s_sc, lds_wave + CHUNK,
                                                lds_wave + 2 * CHUNK, a.lowbits);
         } else {
             wave_lds_sync();
@@ -917,9 +944,13 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, int tq, int *lds_wav
 // without the small-row form: six spilled registers)
 // FIN: the launch's last workgroups finalize the split rows (role_task's note); its own instantiation, so the
 // launches without the role run the kernel they ran before it existed
-template <int VEC, int G, int R, bool FILT, bool OTF, int EPI = 0, bool FS = false, bool FIN = false, typename S = float>
+// BUF: the work-item roles read through buffer resources (agg_fwd_src.h; fp32 tables below 2 GiB - the launcher's rule,
+// fwd_plan.h: fwd_buffer_form); false = the flat form.  The finalize role reads flat in both.
+template <int VEC, int G, int R, bool FILT, bool OTF, int EPI = 0, bool FS = false, bool FIN = false, typename S = float,
+          bool BUF = false>
 __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const FwdArgs a)
 {
+    static_assert(!BUF || std::is_same<S, float>::value, "buffer-addressed reads: fp32 tables");
     static_assert(!(FILT && OTF), "the filter belongs to the table mode");
     static_assert(FILT || !FS, "the small-row filter belongs to the FILT kernel");
     static_assert(std::is_same<S, float>::value || (OTF && EPI == 0), "half rows: on the fly, no store epilogue");
@@ -952,16 +983,17 @@ __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const Fwd
         // share of the chip's wave slots they hold.)
         return;
     }
+    const FwdSrc<BUF, VEC, G, R, S> src(a, lane_id() % G);
     const int nw = a.main_blocks * WAVES;
     const int n_wave_rows = a.n_med_end - a.n_split;
     int it = blockIdx.x * WAVES + wave;
     for (; it < a.n_tasks; it += nw)
-        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN, S>(a, a.task_order[it], lw);
+        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN, S>(a, src, a.task_order[it], lw);
     it -= a.n_tasks;
     for (; it < n_wave_rows; it += nw)
-        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI, S>(a, it, lw);
+        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI, S>(a, src, it, lw);
     it -= n_wave_rows;
-    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS, S>(a, it, nw, nsets, lw);
+    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS, S>(a, src, it, nw, nsets, lw);
 }
 
 }  // namespace sngnn

@@ -1,7 +1,8 @@
 // Instantiates the fused aggregation forward for rows read 1 float(s) per lane.
 #include "agg_fwd_impl.h"
 
-SNGNN_AGG_FWD_TU(float, 1)
+// (the work-item roles in their buffer form; the flat form: agg_fwd_flat_v1.hip)
+SNGNN_AGG_FWD_BUF_TU(1)
 
 namespace sngnn {
 

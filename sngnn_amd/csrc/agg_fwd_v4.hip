@@ -1,7 +1,8 @@
 // Instantiates the fused aggregation forward for rows read 4 float(s) per lane.
 #include "agg_fwd_impl.h"
 
-SNGNN_AGG_FWD_TU(float, 4)
+// (the work-item roles in their buffer form; the flat form: agg_fwd_flat_v4.hip)
+SNGNN_AGG_FWD_BUF_TU(4)
 
 namespace sngnn {
 

@@ -3,6 +3,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <type_traits>
+#include "buffer_addr.h"
 #include "common.h"
 
 namespace sngnn {
@@ -363,6 +364,26 @@ template <int VEC, int G, int R> struct Row {
             } else {
                 const float t = row[cc];
                 x[r][0] = in ? t : 0.f;
+            }
+        }
+    }
+
+    // The same row of an fp32 table named by a buffer resource (buffer_addr.h): off[r] = the lane's byte offset of
+    // its step-r vector in the table, or an out-of-range offset - lanes beyond C, slots nobody reads - which loads
+    // zeros and sends no request: no select behind the load, no 64-bit address in front of it.
+    __device__ __forceinline__ void load_buf(__amdgpu_buffer_rsrc_t table, const unsigned (&off)[R])
+    {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if constexpr (VEC == 4) {
+                const auto t = __builtin_amdgcn_raw_buffer_load_b128(table, off[r], 0, 0);
+                x[r][0] = __uint_as_float(t[0]); x[r][1] = __uint_as_float(t[1]);
+                x[r][2] = __uint_as_float(t[2]); x[r][3] = __uint_as_float(t[3]);
+            } else if constexpr (VEC == 2) {
+                const auto t = __builtin_amdgcn_raw_buffer_load_b64(table, off[r], 0, 0);
+                x[r][0] = __uint_as_float(t[0]); x[r][1] = __uint_as_float(t[1]);
+            } else {
+                x[r][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(table, off[r], 0, 0));
             }
         }
     }

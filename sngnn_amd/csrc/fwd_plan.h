@@ -52,6 +52,19 @@ inline size_t finc_lds_bytes(int C, int max_slots) { return ((size_t)FINC_WAVES_
 constexpr size_t FIN_LDS_SCORES_BUDGET = 120 * 1024;   // partial rows + kept list + as many scores as fit under this
 constexpr size_t FIN_LDS_LIMIT = 150 * 1024;           // the kept list alone beyond this: top_k too large
 
+// ---- how the work-item roles address what they gather (agg_fwd_src.h) ----------------------------------------------
+// The buffer form - a resource per array and a 32-bit byte offset per load, out-of-range offsets for whatever nobody
+// reads - iff the table has fewer than 2^31 bytes: an offset with bit 31 set must be beyond every array a resource
+// names.  index_bytes: the largest of the graph's own arrays the roles read that way (column ids, 4 E'; the small
+// rows' descriptors, 16 N) - below the table's size on every graph but degenerate ones, held to the same limit.
+// addr_mode (sngnn_tuning_set(11, v)): 0 = this rule, 1 = the flat form always (64-bit pointers: the form for the
+// tables beyond the limit, and the reference of an A/B measurement).
+constexpr int64_t FWD_BUFFER_LIMIT = (int64_t)1 << 31;
+inline bool fwd_buffer_form(int64_t table_bytes, int64_t index_bytes, int addr_mode)
+{
+    return addr_mode != 1 && table_bytes < FWD_BUFFER_LIMIT && index_bytes < FWD_BUFFER_LIMIT;
+}
+
 // whether split rows keep chunk-local candidates (else: scores to HBM scratch + k_agg_fin)
 inline bool fwd_use_candidates(int top_k, int C, int max_split_deg)
 {

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "agg_fwd_filter.h"
+#include "buffer_addr.h"
 #include "common.h"
 #include "device_utils.h"
 
@@ -129,12 +130,7 @@ __global__ __launch_bounds__(256) void k_linear_fwd(const float *__restrict__ x,
 // No workgroup barriers.
 // ---------------------------------------------------------------------------
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-constexpr unsigned BUF_OOB = 0x80000000u;       // an offset no table of < 2 GiB contains
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
+// (make_rsrc, BUF_OOB: buffer_addr.h)
 
 // ---- fp32 products on the bf16 matrix cores (BF3 = true) --------------------------------------
 // The fp32 MFMAs (`v_mfma_f32_16x16x4_f32`) are not XDL operations: they run on the vector ALU's
