@@ -1222,7 +1222,9 @@ int sngnn_epilogue_backward(const float *grad, const float *act, float scale, in
  * n = h / max(||h||, 1e-12), the clamped norms and (filt != NULL, C > 32) the fp16 filter rows -
  * bit for bit what sngnn_normalize_rows_filter computes from h (same summation tree, IEEE
  * square root and division), so sngnn_agg_forward_prepared can follow without a normalisation
- * pass.  C % 4 == 0, C <= 64, F in {16, 32, 64, 128} (sngnn_linear_normalized_supported).
+ * pass.  C % 4 == 0, C <= 64, F in {16, 32, 64, 128}, and x, h, the unit rows and the filter rows each
+ * below 2^31 - 64 MiB bytes (sngnn_linear_normalized_supported); beyond: sngnn_linear_forward and a
+ * normalisation pass.
  */
 int sngnn_linear_normalized_supported(int64_t N, int F, int C);
 int sngnn_linear_forward_normalized(const float *x, const float *weight, const float *bias,

@@ -30,7 +30,10 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     } while (0)
 
 // MFMA weight gradient of self.lin (linear.hip), used by sngnn_linear_wgrad (head.hip)
-constexpr int WGRAD_MFMA_WGS = 256;           // persistent workgroups = partial results
+constexpr int WGRAD_MFMA_WGS = 256;           // persistent workgroups = partial results, per slab of rows
+constexpr int64_t WGRAD_MFMA_SLAB = 1 << 20;  // rows a launch takes: 64 16-row blocks a wave at WGRAD_MFMA_WGS workgroups
+// chunk partials beyond which k_sum_partials / k_rep_sum_partials add them in double (a lane's chain is a 16th of them)
+constexpr int WGRAD_WIDE_SUM_CHUNKS = 256;
 int wgrad_mfma_partials(int64_t N, int C, int F);
 int launch_wgrad_mfma(const float *g, const float *x, int64_t N, int C, int F, float *part, float *part_b,
                       hipStream_t st);

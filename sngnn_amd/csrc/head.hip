@@ -413,12 +413,13 @@ __global__ __launch_bounds__(256 * WG_SUB) void k_wgrad_partial(const float *__r
 // out[j] = sum over chunks of part[chunk][j]: 16 threads per output take every 16th
 // chunk, then their sums are added in fixed order (deterministic).  Two independent sums
 // (weight and bias gradient) share one launch: blocks [0, nbA) do A, the rest B.
+template <typename ACC>
 __global__ __launch_bounds__(256) void k_sum_partials(const float *__restrict__ partA, int64_t lenA,
                                                       float *__restrict__ outA, int nbA,
                                                       const float *__restrict__ partB, int64_t lenB,
                                                       float *__restrict__ outB, int nchunks)
 {
-    __shared__ float s[16][16];
+    __shared__ ACC s[16][16];
     const bool second = (int)blockIdx.x >= nbA;
     const float *part = second ? partB : partA;
     float *out = second ? outB : outA;
@@ -426,16 +427,16 @@ __global__ __launch_bounds__(256) void k_sum_partials(const float *__restrict__ 
     const int blk = second ? blockIdx.x - nbA : blockIdx.x;
     const int o = threadIdx.x & 15, q = threadIdx.x >> 4;
     const int64_t j = (int64_t)blk * 16 + o;
-    float a = 0.f;
+    ACC a = 0;
     if (j < len)
-        for (int k = q; k < nchunks; k += 16) a += part[(size_t)k * len + j];
+        for (int k = q; k < nchunks; k += 16) a += (ACC)part[(size_t)k * len + j];
     s[q][o] = a;
     __syncthreads();
     if (q == 0 && j < len) {
-        float t = 0.f;
+        ACC t = 0;
 #pragma unroll
         for (int w = 0; w < 16; ++w) t += s[w][o];
-        out[j] = t;
+        out[j] = (float)t;
     }
 }
 
@@ -568,7 +569,11 @@ extern "C" int sngnn_linear_wgrad(const float *grad_out, const float *x, int64_t
     }
     const int64_t len = (int64_t)C * F;
     const int nbA = (int)((len + 15) / 16), nbB = grad_bias ? (C + 15) / 16 : 0;
-    k_sum_partials<<<nbA + nbB, 256, 0, st>>>(part, len, grad_weight, nbA, part_b, C, grad_bias, chunks);
+    // (many partials: added in double - a lane's fp32 chain over 1 024 of them alone missed the float64 gate at 8.4 M rows)
+    if (chunks > WGRAD_WIDE_SUM_CHUNKS)
+        k_sum_partials<double><<<nbA + nbB, 256, 0, st>>>(part, len, grad_weight, nbA, part_b, C, grad_bias, chunks);
+    else
+        k_sum_partials<float><<<nbA + nbB, 256, 0, st>>>(part, len, grad_weight, nbA, part_b, C, grad_bias, chunks);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }

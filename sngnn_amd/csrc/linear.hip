@@ -618,26 +618,51 @@ static int launch_wgrad_uf(const float *g, const float *x, int N, int C, float *
 }
 
 // number of per-workgroup partials the MFMA weight gradient writes for N rows (0: shape
-// not handled, the caller falls back to k_wgrad_partial)
+// not handled, the caller falls back to k_wgrad_partial).  The rows go in slabs of WGRAD_MFMA_SLAB, one launch of up
+// to WGRAD_MFMA_WGS workgroups each: a wave then carries its fp32 accumulators through 64 16-row blocks at most,
+// however many rows there are (one launch over 4 M rows: 250 blocks a wave, and the rounding of that chain alone was
+// 12 units of 2^-24 x the magnitude at the worst element, tests/test_large_dense_gpu.py).  Up to one slab: one launch,
+// the bits of before.  Beyond, every launch has a tail of its own: measured 0.300 -> 0.344 ms at 2 449 029 x 128 -> 40
+// (three launches) and 0.623 -> 0.688 ms at 4 063 231 x 128 -> 64.  The slab is the size at which a wave's chain is as
+// long as a sum over a few thousand rows - what the float64 gate's reference measures - not the size at which the gate
+// was first seen missed: the error grows with the chain, and how fast depends on the rows.
+static int wgrad_slab_wgs(int64_t rows) { return (int)std::min<int64_t>(WGRAD_MFMA_WGS, (rows + 63) / 64); }
+
 int wgrad_mfma_partials(int64_t N, int C, int F)
 {
     const int64_t lim = ((int64_t)1 << 31) - ((int64_t)64 << 20);
     if (C > 64 || (F != 16 && F != 32 && F != 64 && F != 128)) return 0;
     if (N < 1024 || N * F * 4 >= lim || N * (int64_t)C * 4 >= lim) return 0;
-    return (int)std::min<int64_t>(WGRAD_MFMA_WGS, (N + 63) / 64);
+    const int64_t rest = N % WGRAD_MFMA_SLAB;
+    return (int)(N / WGRAD_MFMA_SLAB * WGRAD_MFMA_WGS) + (rest ? wgrad_slab_wgs(rest) : 0);
+}
+
+template <int UF>
+static int launch_wgrad_slabs(const float *g, const float *x, int64_t N, int C, float *part, float *part_b, hipStream_t st)
+{
+    constexpr int F = 16 * UF;
+    int64_t p0 = 0;
+    for (int64_t r0 = 0; r0 < N; r0 += WGRAD_MFMA_SLAB) {
+        const int64_t rows = std::min<int64_t>(WGRAD_MFMA_SLAB, N - r0);
+        const int nwg = wgrad_slab_wgs(rows);
+        if (int rc = launch_wgrad_uf<UF>(g + r0 * C, x + r0 * F, (int)rows, C, part + p0 * C * F,
+                                         part_b ? part_b + p0 * C : nullptr, nwg, st))
+            return rc;
+        p0 += nwg;
+    }
+    return SNGNN_OK;
 }
 
 int launch_wgrad_mfma(const float *g, const float *x, int64_t N, int C, int F, float *part, float *part_b,
                       hipStream_t st)
 {
-    const int nwg = wgrad_mfma_partials(N, C, F);
-    SN_REQUIRE(nwg > 0, SNGNN_EINVAL, "shape not handled by the MFMA weight gradient");
+    SN_REQUIRE(wgrad_mfma_partials(N, C, F) > 0, SNGNN_EINVAL, "shape not handled by the MFMA weight gradient");
     SN_REQUIRE((uintptr_t)x % 16 == 0, SNGNN_EINVAL, "x must be 16-byte aligned");
     switch (F) {
-    case 16: return launch_wgrad_uf<1>(g, x, (int)N, C, part, part_b, nwg, st);
-    case 32: return launch_wgrad_uf<2>(g, x, (int)N, C, part, part_b, nwg, st);
-    case 64: return launch_wgrad_uf<4>(g, x, (int)N, C, part, part_b, nwg, st);
-    default: return launch_wgrad_uf<8>(g, x, (int)N, C, part, part_b, nwg, st);
+    case 16: return launch_wgrad_slabs<1>(g, x, N, C, part, part_b, st);
+    case 32: return launch_wgrad_slabs<2>(g, x, N, C, part, part_b, st);
+    case 64: return launch_wgrad_slabs<4>(g, x, N, C, part, part_b, st);
+    default: return launch_wgrad_slabs<8>(g, x, N, C, part, part_b, st);
     }
 }
 
@@ -691,12 +716,14 @@ static int launch_linear_rows(const float *x, const float *w, const float *b, in
 using namespace sngnn;
 
 // whether sngnn_linear_forward_normalized handles a shape (else: sngnn_linear_forward + a
-// normalisation pass)
+// normalisation pass).  Every table the kernel addresses through a resource stays below lim: x, the 128-byte filter
+// rows, and h and the unit rows (N C 4 bytes: more than the filter rows at C > 32) - the lanes beyond C of a 16-lane row
+// store at BUF_OOB, which only a table below 2^31 bytes leaves out of range.
 extern "C" int sngnn_linear_normalized_supported(int64_t N, int F, int C)
 {
     const int64_t lim = ((int64_t)1 << 31) - ((int64_t)64 << 20);
     return (C % 4 == 0 && C >= 4 && C <= 64 && (F == 16 || F == 32 || F == 64 || F == 128) && N >= 1 &&
-            N * F * 4 < lim && N * (int64_t)128 < lim)
+            N * F * 4 < lim && N * (int64_t)128 < lim && N * (int64_t)C * 4 < lim)
                ? 1 : 0;
 }
 
