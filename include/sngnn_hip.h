@@ -323,7 +323,11 @@ int sngnn_agg_forward_rows(const sngnn_graph_t *g, const float *n, const float *
  * knob 11 = how the forward's work-item roles address what they gather (table rows, norms, column ids, filter rows):
  * 0 (default) = through buffer resources with 32-bit offsets when the fp32 table has fewer than 2^31 bytes (slots and
  * lanes nobody reads get an out-of-range offset: zeros, no request), the flat form otherwise; 1 = the flat form
- * (64-bit pointers) always.  The same bits either way - the A/B of a measurement, and the path of bigger tables. */
+ * (64-bit pointers) always.  The same bits either way - the A/B of a measurement, and the path of bigger tables;
+ * knob 12 = which main kernel a forward that asks for `out` only runs (wsel, inv_norm, sel_src, sel_w and kept bits
+ * NULL, no epilogue, no head, no row filter; fp32 rows scored from the unit-row table without the fp16 filter):
+ * 0 (default) = the lean instantiation, which compiles the code of those outputs out of every role; 1 = the general
+ * kernel always.  The same bits either way - the A/B of a measurement and of tests/test_fwd_lean_gpu.py. */
 int sngnn_tuning_set(int which, int value);
 /* how many workgroups of the last sngnn_agg_forward* launch on this process finalized split rows (0 = the
  * finalize was a launch of its own, or there was nothing to finalize) - measurement aid, see knob 9 */

@@ -81,6 +81,8 @@ int sngnn::g_fin_inline = 1;
 // sngnn_tuning_set(11, v): how the work-item roles address their gathers - 0 = buffer resources where the table allows
 // (fwd_plan.h: fwd_buffer_form), 1 = the flat form always
 static int g_addr_mode = 0;
+// sngnn_tuning_set(12, v): 0 = calls that want `out` only run the lean main kernel, 1 = the general kernel always
+int sngnn::g_fwd_general_only = 0;
 int sngnn::g_last_fin_blocks = 0;
 extern "C" int sngnn_last_forward_finalize_workgroups(void) { return sngnn::g_last_fin_blocks; }
 // a value no earlier call of this process has used (the finalize role: the tasks' done words)
@@ -92,7 +94,8 @@ unsigned long long sngnn::next_fin_nonce()
 bool sngnn::fwd_scores_on_the_fly_forced() { return g_table_mode == 2; }
 extern "C" int sngnn_tuning_set(int which, int value)
 {
-    SN_REQUIRE(which == 0 || (which >= 2 && which <= 11), SNGNN_EINVAL, "unknown tuning knob");
+    SN_REQUIRE(which == 0 || (which >= 2 && which <= 12), SNGNN_EINVAL, "unknown tuning knob");
+    if (which == 12) { sngnn::g_fwd_general_only = value == 1 ? 1 : 0; return SNGNN_OK; }
     if (which == 11) { g_addr_mode = value == 1 ? 1 : 0; return SNGNN_OK; }
     if (which == 10) return sngnn::set_hist_copies(value);
     if (which == 9) { sngnn::g_fin_inline = value < 0 ? 0 : value; return SNGNN_OK; }

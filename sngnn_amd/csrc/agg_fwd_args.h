@@ -187,6 +187,9 @@ extern int g_prof_reps;
 // sngnn_tuning_set(9, v): 0 = the split rows' finalize as a launch of its own (round 4's form), 1 = inside the main
 // launch when it pays (fwd_plan.h: fwd_fin_blocks), v > 1 = inside it on v workgroups
 extern int g_fin_inline, g_last_fin_blocks;
+// sngnn_tuning_set(12, v): 0 = a call that wants `out` only runs the lean main kernel (agg_fwd_roles.h: k_agg_fwd,
+// LEAN; launch_agg_fwd_impl has the rule), 1 = the general kernel always (the A/B of a measurement; the tests)
+extern int g_fwd_general_only;
 unsigned long long next_fin_nonce();
 
 // The launchers the entry points call (agg_fwd.hip compiles none of the kernels behind them).

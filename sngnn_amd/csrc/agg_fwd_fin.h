@@ -67,7 +67,8 @@ __device__ __forceinline__ void fin_row_head(const FwdArgs &a, int i, int p, con
 
 // The winners of a split row (s_key_w / s_src_w [0, nsel): keys and source ids, in the selection's own order) ->
 // the row's weighted sum, its mean and stores, the bookkeeping of the kept edges.  One wave.
-template <int VEC, int G, int R, bool HEAD, typename S = float>
+// LEAN: the call wants `out` only (k_agg_fwd's note) - no wsel, kept bits or selection lists.
+template <int VEC, int G, int R, bool HEAD, typename S = float, bool LEAN = false>
 __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, int rs, int deg, int t0, int nsel,
                                                 const unsigned long long *s_key_w, const int *s_src_w, int head_yy,
                                                 unsigned head_sv)
@@ -77,7 +78,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
     constexpr int NG = 64 / G;
     const int lane = lane_id();
     const int gid = lane / G, lg = lane % G;
-    const bool emit = a.sel_src != nullptr;
+    const bool emit = !LEAN && a.sel_src != nullptr;
     RowT acc;
     acc.zero();
     constexpr int GU = R >= 3 ? 2 : 4;                        // winner rows in flight per lane group
@@ -97,7 +98,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
             if (w < nsel) acc.axpy(key_score(s_key_w[w]) * nj[u], x[u]);
         }
     }
-    if (lane < nsel) {
+    if (!LEAN && lane < nsel) {
         const unsigned long long kq = s_key_w[lane];
         const float sq = key_score(kq);
         if (a.wsel) a.wsel[rs + key_index(kq)] = sq;
@@ -117,7 +118,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
         head_write_entry(a, a.head_nmain + p, ha);
         return;
     }
-    row_epilogue<VEC, G, R>(a, acc, i, lg);
+    if constexpr (!LEAN) row_epilogue<VEC, G, R>(a, acc, i, lg);
     if (gid == 0) acc.store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
 }
 
@@ -146,7 +147,7 @@ __device__ __forceinline__ void fin_winners_row(const FwdArgs &a, int p, int i, 
 
 // Rows [pb, pb + 64 / G) of at most 128 candidates each, one per lane group.  seen (per group): the row's done
 // words were all read as done by the batch before (the look-ahead below); on return: whether row pb_next + gid's were.
-template <int VEC, int G, int R, typename S = float>
+template <int VEC, int G, int R, typename S = float, bool LEAN = false>
 __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb_next, int *lds_wave, bool &dead,
                                                 bool &seen)
 {
@@ -163,7 +164,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
     const int pc = valid ? p : a.n_split - 1;
     const int4 d = a.rdesc[pc];
     const int i = d.x, rs = d.y, deg = d.z;
-    const bool act = valid && !a.skip_row(i);                 // (group-uniform; a skipped row's tasks skipped it too)
+    const bool act = valid && (LEAN || !a.skip_row(i));       // (group-uniform; a skipped row's tasks skipped it too)
     const int t0 = a.split_task0[pc], t1 = a.split_task0[pc + 1];
     unsigned long long *s_key = reinterpret_cast<unsigned long long *>(lds_wave + gid * FIN_GROUP_WORDS);
     int *s_src = lds_wave + gid * FIN_GROUP_WORDS + 2 * CAND_MAX_K;
@@ -238,8 +239,8 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
         for (int u = 0; u < STEP; ++u)
             if (w0 + u < nsel) part[u % NG].axpy(key_score(s_key[w0 + u]) * nj[u], x[u]);
     }
-    const bool emit = a.sel_src != nullptr;
-    for (int w = lg; w < nsel; w += G) {
+    const bool emit = !LEAN && a.sel_src != nullptr;
+    for (int w = lg; !LEAN && w < nsel; w += G) {
         const unsigned long long kq = s_key[w];
         const float sq = key_score(kq);
         if (a.wsel) a.wsel[rs + key_index(kq)] = sq;
@@ -256,7 +257,7 @@ __device__ __forceinline__ void fin_group_batch(const FwdArgs &a, int pb, int pb
 #pragma unroll
         for (int g = 0; g < NG; g += 2 * m) part[g].add(part[g + m]);
     part[0].div((float)deg);
-    row_epilogue<VEC, G, R>(a, part[0], i, lg);
+    if constexpr (!LEAN) row_epilogue<VEC, G, R>(a, part[0], i, lg);
     if (run) part[0].store(a.outs<S>() + (size_t)i * a.C, a.C, lg);
     seen = fwd_group_bits<G>(__ballot(mine_next), gid) == FULL;
     wave_lds_sync();            // the wave's LDS scratch is reused by its next batch
@@ -324,7 +325,7 @@ __device__ __forceinline__ void fin_stream_row(const FwdArgs &a, int p, int p_ne
 // waves 2, 3 those of row p0 + 1 (none: they only keep the barriers company); the even wave of a pair merges.
 // Called by all waves of the workgroup - every wave passes the same three barriers whatever its row's state.
 // LDS per wave: its winners' keys [0, 64) words | source ids [64, 96) | count [96] | ready flag [97].
-template <int VEC, int G, int R, typename S = float>
+template <int VEC, int G, int R, typename S = float, bool LEAN = false>
 __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_big, int (*lds)[WaveLds<G>::WORDS],
                                                bool &dead)
 {
@@ -337,7 +338,7 @@ __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_b
     const int pc = valid ? p : p0;
     const int4 d = a.rdesc[pc];
     const int i = d.x, rs = d.y, deg = d.z;
-    const bool act = valid && !a.skip_row(i);               // (wave-uniform; a skipped row's tasks skipped it too)
+    const bool act = valid && (LEAN || !a.skip_row(i));     // (wave-uniform; a skipped row's tasks skipped it too)
     const int t0 = a.split_task0[pc], t1 = a.split_task0[pc + 1];
     unsigned long long *s_key_w = reinterpret_cast<unsigned long long *>(lw);
     int *s_src_w = lw + 2 * CAND_MAX_K;
@@ -416,7 +417,7 @@ __device__ __forceinline__ void fin_block_pair(const FwdArgs &a, int p0, int n_b
     const int nfin = __popcll(m0);
     if (k0) { const int o = prefix_popc(m0); s_key_w[o] = key0; s_src_w[o] = src0; }
     wave_lds_sync();
-    fin_winners_row<VEC, G, R, false, S>(a, p, i, rs, deg, t0, nfin, s_key_w, s_src_w, 0, 0u);
+    fin_winners_row<VEC, G, R, false, S, LEAN>(a, p, i, rs, deg, t0, nfin, s_key_w, s_src_w, 0, 0u);
     wave_lds_sync();
 }
 

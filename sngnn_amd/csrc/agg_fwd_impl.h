@@ -132,11 +132,24 @@ int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hi
     g_last_fin_blocks = p.fin_blocks;
     if (fin_inline) a.fin_nonce = next_fin_nonce();
     a.head_nmain = p.head_nmain;
+    // the lean kernel (agg_fwd_roles.h: k_agg_fwd, LEAN): a call that wants `out` and nothing else, where the plain
+    // table-mode kernel would run (fp32 rows, no store epilogue; SNGNN_FWD_PLAIN below); sngnn_tuning_set(12, 1): never
+    [[maybe_unused]] const bool lean = F32 && EPI == 0 && g_fwd_general_only == 0 && a.wsel == nullptr && a.inv_norm == nullptr &&
+                      a.sel_src == nullptr && a.sel_w == nullptr && a.kbits == nullptr && a.head_sel == nullptr &&
+                      a.row_flag == nullptr && a.epi_flags == 0;
     if (ev) SN_HIP(hipEventRecord(ev[0], st));
-#define SNGNN_FWD_LAUNCH(FILTV, OTFV, FSV)                                                              \
-    do {                                                                                              \
-        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true, S, BUF><<<grid, BLOCK, 0, st>>>(a); \
-        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false, S, BUF><<<grid, BLOCK, 0, st>>>(a);           \
+#define SNGNN_FWD_LAUNCH_L(FILTV, OTFV, FSV, LEANV)                                                            \
+    do {                                                                                                       \
+        if (fin_inline) k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, true, S, BUF, LEANV><<<grid, BLOCK, 0, st>>>(a); \
+        else k_agg_fwd<VEC, G, R, FILTV, OTFV, EPI, FSV, false, S, BUF, LEANV><<<grid, BLOCK, 0, st>>>(a);           \
+    } while (0)
+#define SNGNN_FWD_LAUNCH(FILTV, OTFV, FSV) SNGNN_FWD_LAUNCH_L(FILTV, OTFV, FSV, false)
+#define SNGNN_FWD_PLAIN()                                                                                      \
+    do {                                                                                                       \
+        if constexpr (F32 && EPI == 0) {                                                                       \
+            if (lean) { SNGNN_FWD_LAUNCH_L(false, false, false, true); break; }                                \
+        }                                                                                                      \
+        SNGNN_FWD_LAUNCH(false, false, false);                                                                 \
     } while (0)
     for (int rep = 0; rep < reps && grid > 0; ++rep) {
         if (!F32 || a.nrm == nullptr) {                          // OTF: a.n holds the raw rows
@@ -144,12 +157,14 @@ int launch_agg_fwd_impl(const FwdArgs &a0, int max_split_deg, hipEvent_t *ev, hi
         } else if constexpr (F32 && VEC == 4 && G >= 16 && G * R <= 128) {     // the (G, R) that C in 36 .. 512 maps to
             if (a.filt && a.k >= 0 && a.filt_small) SNGNN_FWD_LAUNCH(true, false, true);
             else if (a.filt && a.k >= 0) SNGNN_FWD_LAUNCH(true, false, false);
-            else SNGNN_FWD_LAUNCH(false, false, false);
+            else SNGNN_FWD_PLAIN();
         } else if constexpr (F32) {
-            SNGNN_FWD_LAUNCH(false, false, false);
+            SNGNN_FWD_PLAIN();
         }
     }
+#undef SNGNN_FWD_PLAIN
 #undef SNGNN_FWD_LAUNCH
+#undef SNGNN_FWD_LAUNCH_L
     if (ev) SN_HIP(hipEventRecord(ev[1], st));
     for (int rep = 0; rep < reps && !fin_inline; ++rep)
         if (int rc = launch_split_finalize<VEC, G, R, S>(a, p, st)) return rc;

@@ -91,17 +91,19 @@ __global__ __launch_bounds__(BLOCK) void k_filter_rows(const float *__restrict__
 // out-of-range offset instead of `self`, and skips a slot beyond EVERY row of the set altogether (t0 + u >= dmax is
 // wave-uniform: a scalar branch around the load and the dot) - the sets are dealt by four-degree buckets, so on an
 // arxiv-like graph, where most rows have one or two in-edges, that is half the slots.
-template <int VEC, int G, int R, bool OTF, int EPI, typename S, typename SRC>
+// LEAN (k_agg_fwd's note): the call wants `out` only - no kept bits, no wsel / inv_norm stores, no selection lists.
+template <int VEC, int G, int R, bool OTF, int EPI, typename S, bool LEAN, typename SRC>
 __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src, const int4 d, bool valid,
                                                int *lds_wave, const int *s_col_set)
 {
+    static_assert(!LEAN || (!OTF && EPI == 0), "the lean form: table mode, plain stores");
     using RowT = Row<VEC, G, R>;
     constexpr int U = Unroll<R>::U;
     constexpr int SETW = WaveLds<G>::SETW;
     const int lane = lane_id();
     const int gid = lane / G, lg = lane % G;
     const int i = d.x, rs = d.y, deg = d.z;
-    const bool emit = a.sel_src != nullptr && a.k >= 0;
+    const bool emit = !LEAN && a.sel_src != nullptr && a.k >= 0;
     const bool rank = a.k >= 0 && deg > a.k;
     const bool need_sc = rank || emit;
     const int self = i + a.row_off;
@@ -122,7 +124,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src,
 
     RowT acc;
     acc.zero();
-    unsigned kb = 0u;                 // the row's kept bits (a.kbits)
+    [[maybe_unused]] unsigned kb = 0u;                 // the row's kept bits (a.kbits)
     // one step: NU slots, t0 .. t0 + NU - 1, of every row of the set - their loads first, all in flight together
     auto step = [&](int t0, auto nu_c) __attribute__((always_inline)) {
         constexpr int NU = decltype(nu_c)::value;
@@ -159,8 +161,8 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src,
                 if (!rank) {
                     const bool sel = (a.k < 0) || (s >= a.thr);
                     if (sel) acc.axpy(s * nj[u], x[u]);
-                    if (a.wsel && lg == 0) a.wsel[rs + t0 + u] = sel ? s : SNGNN_UNSELECTED;
-                    if constexpr (!OTF) kb |= sel ? (1u << (t0 + u)) : 0u;     // (group-uniform; table mode only)
+                    if (!LEAN && a.wsel && lg == 0) a.wsel[rs + t0 + u] = sel ? s : SNGNN_UNSELECTED;
+                    if constexpr (!OTF && !LEAN) kb |= sel ? (1u << (t0 + u)) : 0u;     // (group-uniform; table mode only)
                 }
             }
         }
@@ -181,7 +183,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src,
             }
         }
     }
-    if (a.inv_norm && valid && lg == 0) {
+    if (!LEAN && a.inv_norm && valid && lg == 0) {
         if constexpr (OTF) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
         else a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
@@ -233,9 +235,9 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src,
             }
             const bool sel = rk < a.k && se >= a.thr;
             s_w[e] = sel ? se : SNGNN_UNSELECTED;
-            if (rank && a.wsel) a.wsel[rs + e] = sel ? se : SNGNN_UNSELECTED;
+            if (!LEAN && rank && a.wsel) a.wsel[rs + e] = sel ? se : SNGNN_UNSELECTED;
             // (lane lg == 0 runs every iteration any lane of its group runs: it ends with all the bits)
-            if constexpr (!OTF)
+            if constexpr (!OTF && !LEAN)
                 if (rank && a.kbits) kb |= (unsigned)fwd_group_bits<G>(__ballot(sel), gid) << (e - lg);
             if (emit && sel) {
                 a.sel_src[(size_t)i * a.k + rk] = s_col[e];
@@ -259,7 +261,7 @@ __device__ __forceinline__ void small_rows_set(const FwdArgs &a, const SRC &src,
         }
         wave_lds_sync();       // s_sc / s_w are reused by the next set
     }
-    if constexpr (!OTF)
+    if constexpr (!OTF && !LEAN)
         if (a.kbits && valid && lg == 0) reinterpret_cast<unsigned short *>(a.kbits)[i] = (unsigned short)kb;
     if (valid) {
         acc.div((float)max(deg, 1));
@@ -437,7 +439,7 @@ __device__ __forceinline__ void small_rows_set_filt(const FwdArgs &a, const SRC 
 // current one, so a set costs one memory round trip (its feature rows) instead of a
 // chain of three (descriptor -> columns -> rows).
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool OTF, int EPI, bool FS, typename S, typename SRC>
+template <int VEC, int G, int R, bool OTF, int EPI, bool FS, typename S, bool LEAN, typename SRC>
 __device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int set0, int stride, int nsets, int *lds_wave)
 {
     constexpr int RPW = 64 / G;
@@ -449,7 +451,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int
     auto load_desc = [&](int st) -> int4 {
         const int slot = a.n_med_end + st * RPW + gid;
         int4 d = src.desc_if(slot, st < nsets && slot < a.N);
-        if (a.row_flag != nullptr && d.w >= 0 && a.skip_row(d.x)) d = make_int4(0, 0, 0, -1);   // not this pass's row
+        if (!LEAN && a.row_flag != nullptr && d.w >= 0 && a.skip_row(d.x)) d = make_int4(0, 0, 0, -1);   // not this pass's row
         return d;
     };
     // lane l fetches column ids q = l + 64 m of the set: row q / SMALL_T, edge q % SMALL_T
@@ -489,7 +491,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int
         const int4 d_n2 = load_desc(s_n2);
         load_cols(d_nxt, cols);                 // in flight during this set's work
         wave_lds_sync();
-        if (a.row_flag == nullptr || __ballot(d_cur.w >= 0) != 0ull) {
+        if (LEAN || a.row_flag == nullptr || __ballot(d_cur.w >= 0) != 0ull) {
             bool done = false;
             if constexpr (FS && G >= SMALL_T && !OTF) {
                 if (a.filt_small) {                               // (uniform)
@@ -497,7 +499,7 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int
                     done = true;
                 }
             }
-            if (!done) small_rows_set<VEC, G, R, OTF, EPI, S>(a, src, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
+            if (!done) small_rows_set<VEC, G, R, OTF, EPI, S, LEAN>(a, src, d_cur, d_cur.w >= 0, lds_wave, lds_wave + SETW * buf);
         }
         store_cols(cols, lds_wave + SETW * (buf ^ 1));
         d_cur = d_nxt;
@@ -522,12 +524,20 @@ __device__ __forceinline__ void role_small(const FwdArgs &a, const SRC &src, int
 //           except: a streaming edge within delta of thr is scored exactly; with exact_all EVERY
 //           edge is (the paths that rank from scores in HBM scratch: top_k > CAND_MAX_K, hubs
 //           beyond the candidate finalize, ranks of a streaming split row).
-template <int VEC, int G, int R, bool OTF, typename S, typename SRC>
+//   MODE: SCORE_ANY = all of the above decided at run time (wave-uniform tests, per slot); the lean kernel's call sites
+//           say what they know at compile time - SCORE_STREAM: stream, no scores kept (sc, ids_lds unused; no wsel);
+//           SCORE_KEEP: scores to sc (and ids to ids_lds when WITH_IDS), nothing accumulated, no norm loaded - so the
+//           norm load of a slot joins its row load without a branch region between them.
+enum { SCORE_ANY = 0, SCORE_STREAM = 1, SCORE_KEEP = 2 };
+template <int VEC, int G, int R, bool OTF, typename S, int MODE = SCORE_ANY, bool WITH_IDS = false, typename SRC>
 __device__ __forceinline__ void score_edges(const FwdArgs &a, const SRC &src, int self, int rs, int e0, int e1,
                                             const Row<VEC, G, R> &ni, float inv_i, bool stream,
                                             float *sc, int sc_off, Row<VEC, G, R> &acc,
                                             int *ids_lds = nullptr, bool exact_all = false)
 {
+    static_assert(MODE == SCORE_ANY || !OTF, "the compile-time modes: table mode");
+    if constexpr (MODE == SCORE_STREAM) stream = true;
+    if constexpr (MODE == SCORE_KEEP) stream = false;
     using RowT = Row<VEC, G, R>;
     constexpr int NG = 64 / G;
     constexpr int U = Unroll<R>::U;
@@ -587,6 +597,17 @@ __device__ __forceinline__ void score_edges(const FwdArgs &a, const SRC &src, in
                 }
             } else {
                 s = unit_dot<VEC, G, R>(ni, x[u]);
+            }
+            if constexpr (MODE == SCORE_STREAM) {
+                if (act[u] && ((a.k < 0) || (s >= a.thr))) acc.axpy(s * nj[u], x[u]);
+                continue;
+            }
+            if constexpr (MODE == SCORE_KEEP) {
+                if (act[u] & (lg == 0)) {
+                    sc[t[u] - sc_off] = s;
+                    if constexpr (WITH_IDS) ids_lds[t[u] - sc_off] = j[u];
+                }
+                continue;
             }
             if (act[u]) {
                 if (sc && lg == 0) sc[t[u] - sc_off] = s;
@@ -722,9 +743,10 @@ __device__ __forceinline__ WaveSel banded_select(const FwdArgs &a, const SRC &sr
 // ---------------------------------------------------------------------------
 // Class B: SMALL_T < deg <= WAVE_T, one wave per row.
 // ---------------------------------------------------------------------------
-template <int VEC, int G, int R, bool FILT, bool OTF, int EPI, typename S, typename SRC>
+template <int VEC, int G, int R, bool FILT, bool OTF, int EPI, typename S, bool LEAN, typename SRC>
 __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int item, int *lds_wave)
 {
+    static_assert(!LEAN || (!FILT && !OTF && EPI == 0), "the lean form: table mode, no filter, plain stores");
     using RowT = Row<VEC, G, R>;
     constexpr int NG = 64 / G;
     const int lane = lane_id();
@@ -732,9 +754,9 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int 
     const int slot = a.n_split + item;
     const int4 d = a.rdesc[slot];
     const int i = d.x, rs = d.y, deg = d.z;
-    if (a.skip_row(i)) return;                              // (wave-uniform)
+    if (!LEAN && a.skip_row(i)) return;                     // (wave-uniform)
     const int self = i + a.row_off;
-    const bool emit = a.sel_src != nullptr && a.k >= 0;
+    const bool emit = !LEAN && a.sel_src != nullptr && a.k >= 0;
     const bool rank = a.k >= 0 && deg > a.k;
     const bool need_sc = rank || emit;
 
@@ -755,7 +777,11 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int 
     // two-precision selection: the filter for ranking rows; OTF whenever scores are kept (ranks
     // asked for on a streaming row included: their order needs exact scores too)
     const bool banded = OTF ? need_sc : (FILT && rank && deg >= a.filt_min_deg);
-    if (!banded)
+    if constexpr (LEAN) {
+        // (need_sc == rank, never banded: which of the two passes this row takes is known here)
+        if (rank) score_edges<VEC, G, R, false, S, SCORE_KEEP, true>(a, src, self, rs, 0, deg, ni, inv_i, false, s_sc, 0, acc, s_ids);
+        else score_edges<VEC, G, R, false, S, SCORE_STREAM>(a, src, self, rs, 0, deg, ni, inv_i, true, nullptr, 0, acc);
+    } else if (!banded)
         score_edges<VEC, G, R, OTF, S>(a, src, self, rs, 0, deg, ni, inv_i, !rank, need_sc ? s_sc : nullptr, 0, acc,
                                     rank ? s_ids : nullptr);
 
@@ -780,11 +806,11 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int 
         if (ws.kept0) s_list[prefix_popc(m0)] = i0;
         if (ws.kept1) s_list[n0 + prefix_popc(m1)] = i1;
         const int nsel = n0 + __popcll(m1);
-        if ((rank || banded) && a.wsel) {
+        if (!LEAN && (rank || banded) && a.wsel) {
             if (i0 < deg) a.wsel[rs + i0] = ws.kept0 ? s_sc[i0] : SNGNN_UNSELECTED;
             if (i1 < deg) a.wsel[rs + i1] = ws.kept1 ? s_sc[i1] : SNGNN_UNSELECTED;
         }
-        if constexpr (!OTF)
+        if constexpr (!OTF && !LEAN)
             if (a.kbits && lane < 4)          // the row's 128 kept bits at its slot
                 a.kbits[a.kb_wbase + 4 * item + lane] = (unsigned)((lane < 2 ? m0 : m1) >> (32 * (lane & 1)));
         wave_lds_sync();
@@ -831,7 +857,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int 
     }
     // (stored at the END of the row: a store up front would pin the scoring pass's first
     // column-id loads behind it - the pointers are not restrict)
-    if (lane == 0 && a.inv_norm) {
+    if (!LEAN && lane == 0 && a.inv_norm) {
         if constexpr (OTF) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
         else a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
@@ -844,7 +870,7 @@ __device__ __forceinline__ void role_wave(const FwdArgs &a, const SRC &src, int 
 // FIN: the row's finalize runs in THIS launch (fin_block_pair / fin_group_batch / fin_stream_row) - what it reads
 // or overwrites is stored at agent scope, then the task says "done".  The launches whose finalize is the next
 // launch run the FIN = false instantiation: plain stores, the code of round 4.
-template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN, typename S, typename SRC>
+template <int VEC, int G, int R, bool FILT, bool OTF, bool FIN, typename S, bool LEAN, typename SRC>
 __device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int tq, int *lds_wave)
 {
     using RowT = Row<VEC, G, R>;
@@ -853,10 +879,11 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int 
     const int p = a.task_slot[tq], c = a.task_chunk[tq];
     const int4 d = a.rdesc[p];
     const int i = d.x, rs = d.y, deg = d.z;
-    if (a.skip_row(i)) return;                              // (wave-uniform)
+    static_assert(!LEAN || (!FILT && !OTF), "the lean form: table mode, no filter");
+    if (!LEAN && a.skip_row(i)) return;                     // (wave-uniform)
     const int self = i + a.row_off;
     const int e0 = c * CHUNK, e1 = min(deg, e0 + CHUNK);
-    const bool emit = a.sel_src != nullptr && a.k >= 0;
+    const bool emit = !LEAN && a.sel_src != nullptr && a.k >= 0;
     const bool rank = a.k >= 0 && deg > a.k;
     const bool cand = rank && a.use_cand;        // chunk-local top-k -> candidates
 
@@ -868,14 +895,21 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int 
         inv_i = inv_norm_of(q_i);
         if (c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, fmaxf(ieee_sqrt(q_i), EPS_NORM));
     } else {
-        if (c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
+        if (!LEAN && c == 0 && lane == 0 && a.inv_norm) a.inv_norm[i] = ieee_div(1.0f, src.nrm(self));
     }
 
     RowT acc;
     acc.zero();
     float *s_sc = reinterpret_cast<float *>(lds_wave);          // [CHUNK], chunk-local
     float *sc_glb = (!cand && (rank || emit)) ? a.scores + a.split_soff[p] : nullptr;   // HBM scratch
-    if ((FILT || OTF) && cand) { /* scored below, in two precisions */ }
+    if constexpr (LEAN) {
+        // (which pass a task takes is known here: candidates' scores to LDS, a ranking row's to the HBM scratch, or
+        // a streaming row's sum)
+        if (cand) score_edges<VEC, G, R, false, S, SCORE_KEEP>(a, src, self, rs, e0, e1, ni, inv_i, false, s_sc, e0, acc);
+        else if (rank) score_edges<VEC, G, R, false, S, SCORE_KEEP>(a, src, self, rs, e0, e1, ni, inv_i, false, sc_glb, 0, acc);
+        else score_edges<VEC, G, R, false, S, SCORE_STREAM>(a, src, self, rs, e0, e1, ni, inv_i, true, nullptr, 0, acc);
+    }
+    else if ((FILT || OTF) && cand) { /* scored below, in two precisions */ }
     else if (cand) score_edges<VEC, G, R, OTF, S>(a, src, self, rs, e0, e1, ni, inv_i, !rank, s_sc, e0, acc);   // LDS
     // HBM scratch (ranked later from those scores: OTF writes exact ones) / none (pure streaming)
     else score_edges<VEC, G, R, OTF, S>(a, src, self, rs, e0, e1, ni, inv_i, !rank, sc_glb, 0, acc, nullptr,
@@ -904,12 +938,12 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int 
         int32_t *cs = a.cand_src + (size_t)tq * CAND_MAX_K;       // saves the finalize a dependent load
         if (ws.kept0) put(cs + prefix_popc(m0), a.col[rs + e0 + lane]);
         if (ws.kept1) put(cs + n0 + prefix_popc(m1), a.col[rs + e0 + 64 + lane]);
-        if (a.wsel) {     // the finalize overwrites the kept edges of the row
+        if (!LEAN && a.wsel) {     // the finalize overwrites the kept edges of the row
             float *w = a.wsel + rs + e0;
             if (lane < e1 - e0) put(w + lane, SNGNN_UNSELECTED);
             if (lane + 64 < e1 - e0) put(w + lane + 64, SNGNN_UNSELECTED);
         }
-        if constexpr (!OTF)
+        if constexpr (!OTF && !LEAN)
             if (a.kbits && lane < 4) put(a.kbits + a.kb_tbase + 4 * tq + lane, 0u);      // the finalize sets the winners' bits
     } else if (!rank) {
         acc.reduce_across_groups();
@@ -946,10 +980,21 @@ __device__ __forceinline__ void role_task(const FwdArgs &a, const SRC &src, int 
 // launches without the role run the kernel they ran before it existed
 // BUF: the work-item roles read through buffer resources (agg_fwd_src.h; fp32 tables below 2 GiB - the launcher's rule,
 // fwd_plan.h: fwd_buffer_form); false = the flat form.  The finalize role reads flat in both.
+// LEAN: the call wants `out` and nothing else - wsel, inv_norm, sel_src, sel_w and kbits are NULL, no epilogue, no
+// head, no row filter (the benchmark's call; every eval-mode forward of a model) - in table mode on fp32 rows without
+// the fp16 filter (launch_agg_fwd_impl's rule).  What exists only for those outputs - kept-bit words, the stores and
+// their address arithmetic, the selection lists, the wave-uniform tests of the pointers behind them, evaluated per
+// slot - is compiled out of every role, the finalize role included, and the scoring loop knows at compile time which
+// of its passes it is (score_edges: MODE).  The same arithmetic in the same order: the same bits as the general kernel
+// (tests/test_fwd_lean_gpu.py); its own instantiation, so every other call runs the kernel it ran before.
+// (Three further steps were built and measured on top of this and taken out again - select-based straight-line
+// slots, the set's longest row by v_readlane, no division for power-of-two in-degrees: each made the launch with
+// the finalize role slower or moved nothing; profiles/fwd_lean.txt has the series.)
 template <int VEC, int G, int R, bool FILT, bool OTF, int EPI = 0, bool FS = false, bool FIN = false, typename S = float,
-          bool BUF = false>
+          bool BUF = false, bool LEAN = false>
 __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const FwdArgs a)
 {
+    static_assert(!LEAN || (!FILT && !OTF && EPI == 0 && std::is_same<S, float>::value), "the lean form's domain");
     static_assert(!BUF || std::is_same<S, float>::value, "buffer-addressed reads: fp32 tables");
     static_assert(!(FILT && OTF), "the filter belongs to the table mode");
     static_assert(FILT || !FS, "the small-row filter belongs to the FILT kernel");
@@ -975,9 +1020,9 @@ __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const Fwd
             return;
         }
         const int n_big = min(fa.n_split, fa.n_split_gt_wave);
-        for (int p0 = 2 * fb; p0 < n_big; p0 += 2 * nfb) fin_block_pair<VEC, G, R, S>(fa, p0, n_big, lds, dead);
+        for (int p0 = 2 * fb; p0 < n_big; p0 += 2 * nfb) fin_block_pair<VEC, G, R, S, LEAN>(fa, p0, n_big, lds, dead);
         for (int pb = n_big + (fb * WAVES + wave) * RPW; pb < fa.n_split; pb += nfb * WAVES * RPW)
-            fin_group_batch<VEC, G, R, S>(fa, pb, pb + nfb * WAVES * RPW, lw, dead, seen);
+            fin_group_batch<VEC, G, R, S, LEAN>(fa, pb, pb + nfb * WAVES * RPW, lw, dead, seen);
         // (Small-row sets kept back for these waves to take behind their rows - 400 .. 1 600 of 40 383 - moved
         // nothing: 50.9-51.6 us against 51.0; the launch is 6 % slower than without the role's 96 workgroups, the
         // share of the chip's wave slots they hold.)
@@ -988,12 +1033,12 @@ __global__ __launch_bounds__(BLOCK, FWD_WAVES_PER_SIMD) void k_agg_fwd(const Fwd
     const int n_wave_rows = a.n_med_end - a.n_split;
     int it = blockIdx.x * WAVES + wave;
     for (; it < a.n_tasks; it += nw)
-        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN, S>(a, src, a.task_order[it], lw);
+        if (a.role_mask & 1) role_task<VEC, G, R, FILT, OTF, FIN, S, LEAN>(a, src, a.task_order[it], lw);
     it -= a.n_tasks;
     for (; it < n_wave_rows; it += nw)
-        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI, S>(a, src, it, lw);
+        if (a.role_mask & 2) role_wave<VEC, G, R, FILT, OTF, EPI, S, LEAN>(a, src, it, lw);
     it -= n_wave_rows;
-    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS, S>(a, src, it, nw, nsets, lw);
+    if (a.role_mask & 4) role_small<VEC, G, R, OTF, EPI, FS, S, LEAN>(a, src, it, nw, nsets, lw);
 }
 
 }  // namespace sngnn
