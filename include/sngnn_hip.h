@@ -1304,6 +1304,47 @@ int sngnn_segment_mean(const float *val, const int64_t *index, int64_t E, int64_
 int sngnn_sparse_pair_dot(const int64_t *colptr, const int32_t *rowidx, const float *vals,
                           int64_t n_cols, const int64_t *pair_a, const int64_t *pair_b,
                           int64_t n_pairs, float *out, void *stream);
+/*
+ * sparse.py:8-14 with the product kept SPARSE, at any number of columns (csrc/sparse_cosine.hip): S = M_n^T M_n,
+ * M_n the column-normalised [rows, cols] input, coalesced, explicit zeros dropped, in BOTH layouts - by column
+ * (colptr i64 [cols + 1], rowidx i32 ascending inside a column, vals f32) and by row (rowptr i64 [rows + 1],
+ * colidx i32 ascending inside a row, rvals f32); all dev.  Row i of S holds every j that shares a row of M_n with
+ * column i - the structural pattern: the diagonal is an ordinary entry, a sum that cancels to 0.0 stays, a zero
+ * column gives an empty row - column ids ascending, and
+ *     S[i, j] = sum_k M_n[k, i] * M_n[k, j]      k ascending, each product rounded, then added (fp32)
+ * so a value's bits depend on the matrix alone.  One workgroup per row: a row whose candidate bound
+ * sum_{k in col i} deg_row(k) is at most SNGNN_SPARSE_COSINE_HASH_MAX keeps keys and sums in LDS tables (sorted by
+ * key), a larger one in a per-workgroup accumulator of `cols` floats and a bitmap in the workspace.  No
+ * floating-point atomics; the same bits on every run.
+ *   sngnn_sparse_cosine_count   count dev i32 [cols]: the exact number of entries of every row of S
+ *   sngnn_sparse_cosine_fill    offsets dev i64 [cols]: the exclusive scan of count (the caller's), nnz its total;
+ *                               out_col dev i32 [nnz], out_val dev f32 [nnz].  nnz > 2^31 - 1: SNGNN_ERANGE.
+ *   sngnn_sparse_cosine_hist    the same rows, counted instead of stored - the distribution of ALL cols^2 entries of
+ *                               S (diagonal != 0) or of its cols (cols - 1) off-diagonal ones (diagonal == 0), with
+ *                               edges / bins / counts [bins + 2] / stats [3] as in sngnn_cosine_hist (one group):
+ *                               numpy's bin rule against the table itself, on exactly the fp32 values the fill
+ *                               stores; the entries outside the pattern are exact zeros, added arithmetically to
+ *                               the slot that holds 0.0 and counted in min and max.  No limit on nnz.
+ *   workspace, workspace_bytes  the matching sngnn_sparse_cosine_*_workspace_bytes(rows, cols[, bins]) at least
+ *                               (less: SNGNN_EINVAL); cleared by each call.
+ * rows, cols < 2^31 - 1 (SNGNN_ERANGE); NULL or a bad shape: SNGNN_EINVAL.  Refused calls launch nothing.  All
+ * three only enqueue.
+ */
+#define SNGNN_SPARSE_COSINE_HASH_MAX 2048
+int64_t sngnn_sparse_cosine_count_workspace_bytes(int64_t rows, int64_t cols);
+int64_t sngnn_sparse_cosine_fill_workspace_bytes(int64_t rows, int64_t cols);
+int64_t sngnn_sparse_cosine_hist_workspace_bytes(int64_t rows, int64_t cols, int bins);
+int sngnn_sparse_cosine_count(const int64_t *colptr, const int32_t *rowidx, const int64_t *rowptr,
+                              const int32_t *colidx, int64_t rows, int64_t cols, int32_t *count, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+int sngnn_sparse_cosine_fill(const int64_t *colptr, const int32_t *rowidx, const float *vals, const int64_t *rowptr,
+                             const int32_t *colidx, const float *rvals, int64_t rows, int64_t cols,
+                             const int64_t *offsets, int64_t nnz, int32_t *out_col, float *out_val, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+int sngnn_sparse_cosine_hist(const int64_t *colptr, const int32_t *rowidx, const float *vals, const int64_t *rowptr,
+                             const int32_t *colidx, const float *rvals, int64_t rows, int64_t cols, const float *edges,
+                             int bins, int diagonal, unsigned long long *counts, double *stats, void *workspace,
+                             int64_t workspace_bytes, void *stream);
 
 /*
  * kNN similarity graph (the north star's "Node-Similarity build"):

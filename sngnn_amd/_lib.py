@@ -22,6 +22,7 @@ UNSELECTED = -4.0
 LOOPS_REPLACE = 2      # SNGNN_LOOPS_REPLACE: drop the original loops, then append one per node
 MAX_CHANNELS = 512
 TWO_HOP_HASH_MAX = 1024    # SNGNN_TWO_HOP_HASH_MAX: the widest candidate bound the two-hop build keeps in an LDS table
+SPARSE_COSINE_HASH_MAX = 2048    # SNGNN_SPARSE_COSINE_HASH_MAX: the same bound for the sparse cosine's LDS tables
 
 _vp, _i64, _i32, _f32, _f64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double
 
@@ -38,25 +39,20 @@ SIGNATURES = {
     "sngnn_graph_copy_array": (_i32, [_vp, _i32, _vp]),
     "sngnn_graph_array_dev": (_vp, [_vp, _i32]), "sngnn_graph_array_len": (_i64, [_vp, _i32]),
     "sngnn_agg_forward": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sngnn_normalize_rows": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]),
-    "sngnn_filter_row_bytes": (_i64, [_i32]),
+    "sngnn_normalize_rows": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp]), "sngnn_filter_row_bytes": (_i64, [_i32]),
     "sngnn_normalize_rows_filter": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_agg_forward_prepared": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_forward_epilogue": (_i32, [_vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_forward_prepared_epilogue": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sngnn_filter_enable": (_i32, [_i32]),
-    "sngnn_filter_wanted": (_i32, [_vp, _i32, _i32, _f32]),
+    "sngnn_filter_enable": (_i32, [_i32]), "sngnn_filter_wanted": (_i32, [_vp, _i32, _i32, _f32]),
     "sngnn_agg_forward_rows": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "sngnn_tuning_set": (_i32, [_i32, _i32]),
-    "sngnn_last_forward_finalize_workgroups": (_i32, []),
+    "sngnn_tuning_set": (_i32, [_i32, _i32]), "sngnn_last_forward_finalize_workgroups": (_i32, []),
     "sngnn_filter_pair_scores": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_agg_forward_normalized": (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_backward": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_backward_topk": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "sngnn_agg_kept_bits_supported": (_i32, [_vp, _i32, _i32]),
-    "sngnn_agg_head_supported": (_i32, [_vp, _i32, _i32]),
-    "sngnn_agg_head_workspace_bytes": (_i64, [_vp]),
-    "sngnn_graph_kept_bits_bytes": (_i64, [_vp]),
+    "sngnn_agg_kept_bits_supported": (_i32, [_vp, _i32, _i32]), "sngnn_agg_head_supported": (_i32, [_vp, _i32, _i32]),
+    "sngnn_agg_head_workspace_bytes": (_i64, [_vp]), "sngnn_graph_kept_bits_bytes": (_i64, [_vp]),
     "sngnn_agg_backward_bits": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_agg_forward_half": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_agg_backward_half": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -129,8 +125,7 @@ SIGNATURES = {
     "sngnn_head_nll_blend": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_linear_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "sngnn_linear_forward_masked": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _f32, _vp, _vp]),
-    "sngnn_epilogue_backward": (_i32, [_vp, _vp, _f32, _i64, _vp, _vp]),
-    "sngnn_linear_normalized_supported": (_i32, [_i64, _i32, _i32]),
+    "sngnn_epilogue_backward": (_i32, [_vp, _vp, _f32, _i64, _vp, _vp]), "sngnn_linear_normalized_supported": (_i32, [_i64, _i32, _i32]),
     "sngnn_linear_forward_normalized": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_linear_wgrad_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "sngnn_linear_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -138,9 +133,13 @@ SIGNATURES = {
     "sngnn_cosine_class_sums": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_cosine_hist_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "sngnn_cosine_hist": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "sngnn_edge_cosine": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]),
-    "sngnn_segment_mean": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "sngnn_edge_cosine": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]), "sngnn_segment_mean": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sngnn_sparse_pair_dot": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "sngnn_sparse_cosine_count_workspace_bytes": (_i64, [_i64, _i64]), "sngnn_sparse_cosine_fill_workspace_bytes": (_i64, [_i64, _i64]),
+    "sngnn_sparse_cosine_hist_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "sngnn_sparse_cosine_count": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "sngnn_sparse_cosine_fill": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "sngnn_sparse_cosine_hist": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "sngnn_replica_unpack": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_replica_wgrad_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "sngnn_replica_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
