@@ -1325,15 +1325,25 @@ int sngnn_sparse_pair_dot(const int64_t *colptr, const int32_t *rowidx, const fl
  *                               numpy's bin rule against the table itself, on exactly the fp32 values the fill
  *                               stores; the entries outside the pattern are exact zeros, added arithmetically to
  *                               the slot that holds 0.0 and counted in min and max.  No limit on nnz.
- *   workspace, workspace_bytes  the matching sngnn_sparse_cosine_*_workspace_bytes(rows, cols[, bins]) at least
+ *   sngnn_sparse_cosine_topk    the same rows, selected instead of stored - the structural kNN graph, sngnn_knn_graph's
+ *                               sibling: for every column i the k best of the entries the fill would store for row
+ *                               i (the pattern only: a column outside it is no candidate, whatever the sign of the
+ *                               entries; a sum that cancelled to 0.0 is one; (i, i) is one unless exclude_self != 0),
+ *                               in the order (value descending, column id ascending), with the fill's fp32 values
+ *                               bit for bit.  nbr_idx dev i32 [cols, k], nbr_sim dev f32 [cols, k]; a row with
+ *                               fewer than k candidates is padded with -1 / 0.0 (a zero column: k pads).
+ *                               1 <= k <= 32, else SNGNN_EINVAL.  A stored value is never -0.0 (the sums start at
+ *                               +0.0), so the order of the values is the order of the floats.
+ *   workspace, workspace_bytes  the matching sngnn_sparse_cosine_*_workspace_bytes(rows, cols[, bins | k]) at least
  *                               (less: SNGNN_EINVAL); cleared by each call.
  * rows, cols < 2^31 - 1 (SNGNN_ERANGE); NULL or a bad shape: SNGNN_EINVAL.  Refused calls launch nothing.  All
- * three only enqueue.
+ * four only enqueue.
  */
 #define SNGNN_SPARSE_COSINE_HASH_MAX 2048
 int64_t sngnn_sparse_cosine_count_workspace_bytes(int64_t rows, int64_t cols);
 int64_t sngnn_sparse_cosine_fill_workspace_bytes(int64_t rows, int64_t cols);
 int64_t sngnn_sparse_cosine_hist_workspace_bytes(int64_t rows, int64_t cols, int bins);
+int64_t sngnn_sparse_cosine_topk_workspace_bytes(int64_t rows, int64_t cols, int k);
 int sngnn_sparse_cosine_count(const int64_t *colptr, const int32_t *rowidx, const int64_t *rowptr,
                               const int32_t *colidx, int64_t rows, int64_t cols, int32_t *count, void *workspace,
                               int64_t workspace_bytes, void *stream);
@@ -1344,6 +1354,10 @@ int sngnn_sparse_cosine_fill(const int64_t *colptr, const int32_t *rowidx, const
 int sngnn_sparse_cosine_hist(const int64_t *colptr, const int32_t *rowidx, const float *vals, const int64_t *rowptr,
                              const int32_t *colidx, const float *rvals, int64_t rows, int64_t cols, const float *edges,
                              int bins, int diagonal, unsigned long long *counts, double *stats, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+int sngnn_sparse_cosine_topk(const int64_t *colptr, const int32_t *rowidx, const float *vals, const int64_t *rowptr,
+                             const int32_t *colidx, const float *rvals, int64_t rows, int64_t cols, int k,
+                             int exclude_self, int32_t *nbr_idx, float *nbr_sim, void *workspace,
                              int64_t workspace_bytes, void *stream);
 
 /*

@@ -136,10 +136,10 @@ SIGNATURES = {
     "sngnn_edge_cosine": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]), "sngnn_segment_mean": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sngnn_sparse_pair_dot": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_sparse_cosine_count_workspace_bytes": (_i64, [_i64, _i64]), "sngnn_sparse_cosine_fill_workspace_bytes": (_i64, [_i64, _i64]),
-    "sngnn_sparse_cosine_hist_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "sngnn_sparse_cosine_hist_workspace_bytes": (_i64, [_i64, _i64, _i32]), "sngnn_sparse_cosine_topk_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "sngnn_sparse_cosine_count": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "sngnn_sparse_cosine_fill": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
-    "sngnn_sparse_cosine_hist": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "sngnn_sparse_cosine_hist": (_i32, [_vp] * 6 + [_i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]), "sngnn_sparse_cosine_topk": (_i32, [_vp] * 6 + [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "sngnn_replica_unpack": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sngnn_replica_wgrad_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "sngnn_replica_wgrad": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -150,6 +150,13 @@ __device__ __forceinline__ unsigned long long sel_key(float s, unsigned idx)
 {
     return ((unsigned long long)f2key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
 }
+// ... and back: the score's bits and the position of a key
+__device__ __forceinline__ float sel_key_score(unsigned long long key)
+{
+    const unsigned u = (unsigned)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+__device__ __forceinline__ unsigned sel_key_index(unsigned long long key) { return 0xFFFFFFFFu - (unsigned)key; }
 
 // ---------------------------------------------------------------------------
 // Wave-level top-k of selection keys (sel_key above; 0 = no key), NK per lane: bitwise search for

@@ -23,10 +23,24 @@
 // (integer atomics), written per workgroup to a table in the workspace and added by a last launch, which also adds the
 // cols^2 - nnz structural zeros arithmetically.  Sums: per thread over the sorted row in slot order, threads, waves and
 // workgroups in fixed trees, f64 - the same bits on every run.
+//
+// A fourth epilogue, SC_TOPK, selects: the k best entries of the row in the order (value descending, column id
+// ascending) - knn.hip's rule and the aggregation's - as 64-bit keys (sel_key: the order-preserving word of the value in
+// the high half, the complemented id in the low half; keys of one row are unique, so "the k largest" is one set whatever
+// the order they are met in).  The accumulators start at +0.0f (the tables' `tv[s] = 0.f`, the workspace's memset and the
+// `acc[j] = 0.f` of the read-and-clear) and x + p is -0.0 only where both are: a stored value is never -0.0, the order
+// of the keys is the order of the floats.  The selection is a search for the k-th largest key over (id, sum) slots in
+// LDS, one ballot count of the whole workgroup per bit, the value word first and left as soon as a prefix separates
+// exactly k keys (sc_select).  Table path: over the table's slots as the inserts left them - the keys carry the ids, so
+// the by-key sort of the store is not needed.  Accumulator path: `tab` / `tv` are free there and hold a candidate
+// buffer of SC_TABLE_MAX slots; the read-and-clear goes over 64 words a step (four threads a word: at most
+// SC_HASH_MAX entries), appends what beats the running threshold - the k-th key so far - and, when fewer than
+// SC_HASH_MAX slots are free, the buffer is reduced to its k largest and the threshold raised.
 #include <algorithm>
 #include <string>
 
 #include "common.h"
+#include "device_utils.h"
 #include "ws_layout.h"
 
 namespace sngnn {
@@ -39,7 +53,9 @@ constexpr int SC_EMPTY = 0x7fffffff;                              // (column ids
 constexpr int SC_MAX_WGS = 2048;
 constexpr int64_t SC_ACC_BUDGET = (int64_t)512 << 20;             // bytes of accumulators: fewer workgroups at large N
 constexpr int SC_MAX_BINS = 1024;
-enum { SC_COUNT = 0, SC_FILL = 1, SC_HIST = 2 };
+constexpr int SC_MAX_K = 32;                                      // knn.hip's KNN_MAX_K
+constexpr int SC_WAVE_KEYS = 4;                                   // keys a lane holds where one wave selects
+enum { SC_COUNT = 0, SC_FILL = 1, SC_HIST = 2, SC_TOPK = 3 };
 static_assert((SC_WAVES & (SC_WAVES - 1)) == 0, "the waves' classes of j are j & (SC_WAVES - 1)");
 
 // words of one workgroup's bitmap: whole 128-byte lines, so no two workgroups share one; its accumulator has a float
@@ -62,7 +78,7 @@ static ScLayout sc_layout(int64_t cols, int mode, int bins)
     L.wgs = sc_workgroups(cols);
     L.words = sc_words(cols);
     L.acc = up256(L.wgs * L.words * 4);
-    L.cnt = L.acc + (mode == SC_COUNT ? 0 : up256(L.wgs * L.words * 32 * 4));
+    L.cnt = L.acc + (mode == SC_COUNT ? 0 : up256(L.wgs * L.words * 32 * 4));      // (the selection's workspace: the fill's)
     L.psum = L.cnt + (mode == SC_HIST ? up256((int64_t)L.wgs * (bins + 2) * 8) : 0);
     L.pmin = L.psum + (mode == SC_HIST ? up256((int64_t)L.wgs * 8) : 0);
     L.pmax = L.pmin + (mode == SC_HIST ? up256((int64_t)L.wgs * 4) : 0);
@@ -79,6 +95,7 @@ struct ScArgs {
     const int64_t *offs; int32_t *out_col; float *out_val;                // SC_FILL
     const float *edges; int bins, diagonal;                               // SC_HIST
     unsigned long long *wg_cnt; double *psum; float *pmin, *pmax;
+    int k, exclude_self; int32_t *nbr_idx; float *nbr_sim;                // SC_TOPK
 };
 
 // exclusive prefix of c over the workgroup's threads and the total (sh: SC_WAVES words of LDS; two barriers)
@@ -120,10 +137,98 @@ __device__ __forceinline__ int sc_bin(float v, const float *s_edge, int bins, fl
     return b;
 }
 
+// The k largest keys of the slots [0, n) of (tab, tv) - a slot that is empty or holds column `skip` has no key - into
+// top[] in no particular order; returns their number m <= k.  thr: a key that exactly the kept ones reach when the
+// workgroup searched and there were more than k (then m == k), else 0 - the weakest threshold.  The whole workgroup calls it behind a barrier that follows the slots'
+// writes, and leaves it behind one.  A count is one ballot per 256 slots and wave and one barrier (cnt[2][SC_WAVES],
+// used in turn: a wave that writes a pair again has passed the barrier behind every wave's read of it).  The search is
+// wave_topk_keys_n's: the bits of the value word from the top, left at the first prefix that exactly k keys reach; the
+// `lowbits` bits of the id only when equal values lie on both sides of the cut.  Up to 64 SC_WAVE_KEYS slots are wave
+// 0's alone - that function itself, no barrier per step.
+__device__ __forceinline__ int sc_select(const int *tab, const float *tv, int n, int skip, int k, int lowbits,
+                                         unsigned long long *top, int *ntop, int (*cnt)[SC_WAVES],
+                                         unsigned long long &thr)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    auto key_at = [&](int s) -> unsigned long long {
+        if (s >= n) return 0ull;
+        const int j = tab[s];
+        return j == SC_EMPTY || j == skip ? 0ull : sel_key(tv[s], (unsigned)j);
+    };
+    thr = 0ull;
+    if (n <= 64 * SC_WAVE_KEYS) {
+        // few slots - most rows of a sparse graph: wave 0 holds them all and searches with ballots alone
+        if (wave == 0) {
+            unsigned long long key[SC_WAVE_KEYS];
+            bool kept[SC_WAVE_KEYS];
+#pragma unroll
+            for (int q = 0; q < SC_WAVE_KEYS; ++q) key[q] = key_at(64 * q + lane);
+            wave_topk_keys_n<SC_WAVE_KEYS>(key, k, lowbits, kept);
+            int m = 0;
+#pragma unroll
+            for (int q = 0; q < SC_WAVE_KEYS; ++q) {
+                const unsigned long long mask = __ballot(kept[q]);
+                if (kept[q]) top[m + prefix_popc(mask)] = key[q];
+                m += __popcll(mask);
+            }
+            if (lane == 0) *ntop = m;
+        }
+        __syncthreads();
+        const int m = *ntop;
+        __syncthreads();
+        return m;
+    }
+    int turn = 0;
+    auto count = [&](auto pred) -> int {
+        int c = 0;
+        for (int s0 = 0; s0 < n; s0 += SC_BLOCK) c += __popcll(__ballot(pred(key_at(s0 + tid))));
+        int *mine = cnt[turn];
+        turn ^= 1;
+        if (lane == 0) mine[wave] = c;
+        __syncthreads();
+        int t = 0;
+#pragma unroll
+        for (int w = 0; w < SC_WAVES; ++w) t += mine[w];
+        return t;
+    };
+    if (tid == 0) *ntop = 0;
+    unsigned long long T = 1ull;                                  // (every key reaches it)
+    if (count([](unsigned long long q) { return q != 0ull; }) > k) {
+        unsigned Th = 0u;
+        bool cut = false;
+        for (int b = 31; b >= 0 && !cut; --b) {
+            const unsigned cand = Th | (1u << b);
+            const int c = count([cand](unsigned long long q) { return (unsigned)(q >> 32) >= cand; });
+            if (c >= k) { Th = cand; cut = c == k; }
+        }
+        T = (unsigned long long)Th << 32;
+        if (!cut) {                                               // equal values on both sides of the cut: the id decides
+            T |= 0xFFFFFFFFull & ~((1ull << lowbits) - 1ull);
+            for (int b = lowbits - 1; b >= 0; --b) {
+                const unsigned long long cand = T | (1ull << b);
+                const int c = count([cand](unsigned long long q) { return q >= cand; });
+                if (c >= k) { T = cand; if (c == k) break; }
+            }
+        }
+        thr = T;
+    }
+    for (int s0 = 0; s0 < n; s0 += SC_BLOCK) {
+        const unsigned long long q = key_at(s0 + tid);
+        if (q != 0ull && q >= T) {
+            const int p = atomicAdd(ntop, 1);                     // (their order is not the result's: the ranks are)
+            if (p < SC_MAX_K) top[p] = q;
+        }
+    }
+    __syncthreads();
+    const int m = min(*ntop, k);
+    __syncthreads();
+    return m;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
 {
-    constexpr bool NUM = MODE != SC_COUNT, HIST = MODE == SC_HIST;
+    constexpr bool NUM = MODE != SC_COUNT, HIST = MODE == SC_HIST, TOPK = MODE == SC_TOPK;
     __shared__ int tab[SC_TABLE_MAX];
     __shared__ float tv[NUM ? SC_TABLE_MAX : 1];
     __shared__ int sh[SC_WAVES];
@@ -131,6 +236,8 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
     __shared__ unsigned long long s_cnt[HIST ? SC_MAX_BINS + 2 : 1];
     __shared__ float s_mn[SC_WAVES], s_mx[SC_WAVES];
     __shared__ double s_sm[SC_WAVES];
+    __shared__ unsigned long long s_top[TOPK ? SC_MAX_K : 1];
+    __shared__ int s_ntop, s_c[2][SC_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned *bm = a.bitmaps + (size_t)blockIdx.x * a.words;
     float *acc = NUM ? a.acc + (size_t)blockIdx.x * a.words * 32 : nullptr;
@@ -150,6 +257,27 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
         vmin = fminf(vmin, v);
         vmax = fmaxf(vmax, v);
         vsum += (double)v;
+    };
+
+    // the selection's epilogue for row i: the m keys of s_top at their ranks, pads behind them
+    int lowbits = 1;
+    if constexpr (TOPK)
+        while (lowbits < 31 && (1 << lowbits) < a.cols) ++lowbits;
+    auto emit = [&](int i, int m) {
+        if (tid < a.k) {
+            const int64_t o = (int64_t)i * a.k;
+            if (tid < m) {
+                const unsigned long long q = s_top[tid];
+                int rk = 0;
+                for (int u = 0; u < m; ++u) rk += s_top[u] > q ? 1 : 0;
+                a.nbr_idx[o + rk] = (int32_t)sel_key_index(q);
+                a.nbr_sim[o + rk] = sel_key_score(q);
+            } else {
+                a.nbr_idx[o + tid] = -1;
+                a.nbr_sim[o + tid] = 0.f;
+            }
+        }
+        __syncthreads();                                          // (s_top is the next row's too)
     };
 
     for (int i = blockIdx.x; i < a.cols; i += gridDim.x) {
@@ -196,8 +324,10 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
         };
         int total = 0;
         const int64_t off = MODE == SC_FILL ? a.offs[i] : 0;
+        const int skip = TOPK && a.exclude_self != 0 ? i : -1;
         if (cb == 0) {
             // a zero column: an empty row
+            if constexpr (TOPK) emit(i, 0);
         } else if (cb <= SC_HASH_MAX) {
             int T = 64;
             while (T < 2 * cb) T <<= 1;
@@ -227,6 +357,9 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
                 int c = 0;
                 for (int s = tid; s < T; s += SC_BLOCK) c += tab[s] != SC_EMPTY ? 1 : 0;
                 sc_block_scan(c, sh, total);
+            } else if constexpr (TOPK) {
+                unsigned long long thr;
+                emit(i, sc_select(tab, tv, T, skip, a.k, lowbits, s_top, &s_ntop, s_c, thr));
             } else {
                 // bitonic sort by key, ascending, the sums carried along: the entries in front, empty slots behind
                 for (int k = 2; k <= T; k <<= 1)
@@ -273,6 +406,51 @@ __global__ __launch_bounds__(SC_BLOCK) void k_sparse_cosine(ScArgs a)
             } mark{bm, acc};
             walk(mark);
             __syncthreads();
+            if constexpr (TOPK) {
+                // read and clear in word order, 64 words a step: thread t has byte t & 3 of word w0 + (t >> 2), so the
+                // ids ascend with t and a step appends at most 64 * 32 = SC_HASH_MAX entries, which are free
+                int fill = 0;
+                unsigned long long thr = 0ull;
+                for (int w0 = 0; w0 < a.words; w0 += SC_BLOCK / 4) {
+                    const int w = w0 + (tid >> 2);
+                    unsigned bits = (tid & 3) == 0 && w < a.words ? atomicExch(&bm[w], 0u) : 0u;
+                    bits = (__shfl(bits, lane & ~3, 64) >> (8 * (tid & 3))) & 0xFFu;
+                    unsigned long long ck[8];
+                    int np = 0;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) {
+                        ck[b] = 0ull;
+                        if (bits >> b & 1u) {
+                            const int j = w * 32 + 8 * (tid & 3) + b;
+                            const unsigned long long q = sel_key(acc[j], (unsigned)j);
+                            acc[j] = 0.f;
+                            if (j != skip && q > thr) { ck[b] = q; ++np; }
+                        }
+                    }
+                    int chunk;
+                    int p = fill + sc_block_scan(np, sh, chunk);
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        if (ck[b] != 0ull) {
+                            tab[p] = (int)sel_key_index(ck[b]);
+                            tv[p] = sel_key_score(ck[b]);
+                            ++p;
+                        }
+                    fill += chunk;
+                    __syncthreads();
+                    if (SC_TABLE_MAX - fill < SC_HASH_MAX) {
+                        const int m = sc_select(tab, tv, fill, skip, a.k, lowbits, s_top, &s_ntop, s_c, thr);
+                        if (tid < m) {
+                            tab[tid] = (int)sel_key_index(s_top[tid]);
+                            tv[tid] = sel_key_score(s_top[tid]);
+                        }
+                        fill = m;
+                        __syncthreads();
+                    }
+                }
+                emit(i, sc_select(tab, tv, fill, skip, a.k, lowbits, s_top, &s_ntop, s_c, thr));
+                continue;
+            }
             // read and clear in word order (an exchange: it reads where the atomics above wrote)
             for (int w0 = 0; w0 < a.words; w0 += SC_BLOCK) {
                 const int w = w0 + tid;
@@ -428,6 +606,12 @@ extern "C" int64_t sngnn_sparse_cosine_hist_workspace_bytes(int64_t rows, int64_
     return cols < 0 || bins < 1 || bins > SC_MAX_BINS ? 0 : sc_layout(cols, SC_HIST, bins).total;
 }
 
+extern "C" int64_t sngnn_sparse_cosine_topk_workspace_bytes(int64_t rows, int64_t cols, int k)
+{
+    (void)rows;
+    return cols < 0 || k < 1 || k > SC_MAX_K ? 0 : sc_layout(cols, SC_TOPK, 0).total;
+}
+
 extern "C" int sngnn_sparse_cosine_count(const int64_t *colptr, const int32_t *rowidx, const int64_t *rowptr,
                                          const int32_t *colidx, int64_t rows, int64_t cols, int32_t *count,
                                          void *workspace, int64_t workspace_bytes, void *stream)
@@ -492,6 +676,27 @@ extern "C" int sngnn_sparse_cosine_hist(const int64_t *colptr, const int32_t *ro
     const unsigned long long entries = (unsigned long long)cols * (unsigned long long)(diagonal != 0 ? cols : cols - 1);
     k_sc_hist_final<<<1, 1024, 0, st>>>(a.wg_cnt, L.wgs, a.pmin, a.pmax, a.psum, edges, bins, cols > 0 ? entries : 0ull,
                                         counts, stats);
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+extern "C" int sngnn_sparse_cosine_topk(const int64_t *colptr, const int32_t *rowidx, const float *vals,
+                                        const int64_t *rowptr, const int32_t *colidx, const float *rvals, int64_t rows,
+                                        int64_t cols, int k, int exclude_self, int32_t *nbr_idx, float *nbr_sim,
+                                        void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = sc_check(colptr, rowidx, rowptr, colidx, rows, cols)) return rc;
+    SN_REQUIRE(k >= 1 && k <= SC_MAX_K, SNGNN_EINVAL, "k must be in [1, " + std::to_string(SC_MAX_K) + "]");
+    if (cols == 0) return SNGNN_OK;
+    SN_REQUIRE(nbr_idx && nbr_sim, SNGNN_EINVAL, "NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const ScLayout L = sc_layout(cols, SC_TOPK, 0);
+    ScArgs a{};
+    a.colptr = colptr; a.rowidx = rowidx; a.vals = vals; a.rowptr = rowptr; a.colidx = colidx; a.rvals = rvals;
+    a.k = k; a.exclude_self = exclude_self != 0 ? 1 : 0; a.nbr_idx = nbr_idx; a.nbr_sim = nbr_sim;
+    a.diagonal = 1;
+    if (int rc = sc_bind(a, L, cols, workspace, workspace_bytes, st)) return rc;
+    k_sparse_cosine<SC_TOPK><<<L.wgs, SC_BLOCK, 0, st>>>(a);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }

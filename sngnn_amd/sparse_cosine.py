@@ -78,6 +78,41 @@ def cosine_similarity_sparse_csr(mat, device=None) -> torch.Tensor:
     return torch.sparse_csr_tensor(crow.to(torch.int32), col, val, size=(n_cols, n_cols))
 
 
+KNN_MAX_K = 32          # the widest selection of ``sngnn_sparse_cosine_topk`` (and of ``sngnn_knn_graph``)
+
+
+def knn_graph_sparse(mat, k: int, exclude_self: bool = True, device=None):
+    """``toolbox.knn_graph``'s sibling for the sparse input - the STRUCTURAL kNN graph: for every column the ``k``
+    columns of largest shared-neighbour cosine, selected from the rows of ``cosine_similarity_sparse_csr`` as they are
+    built (``sngnn_sparse_cosine_topk``), none of them stored.  Candidates are the entries of the pattern only - a
+    column that shares no row is none, a sum that cancelled to 0.0 is one, (i, i) is one unless ``exclude_self`` - in
+    the order (value descending, column id ascending), with the CSR's fp32 values bit for bit.  Returns
+    (idx int64 [cols, k] in rank order, -1 padded; sim fp32 [cols, k], 0 padded), as ``knn_graph``.  With a
+    ``sparse_columns(mat)`` made beforehand the call only enqueues and can be captured in a graph."""
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be in [1, {KNN_MAX_K}]")
+    sp = sparse_columns(mat, device)
+    colptr, rowidx, vals, rowptr, colidx, rvals = sp.layouts
+    n_rows, n_cols = sp.shape
+    idx = torch.empty((n_cols, k), dtype=torch.int32, device=sp.device)
+    sim = torch.empty((n_cols, k), dtype=torch.float32, device=sp.device)
+    nb = _lib.load().sngnn_sparse_cosine_topk_workspace_bytes(n_rows, n_cols, k)
+    _lib.call("sngnn_sparse_cosine_topk", sp.device, colptr, rowidx, vals, rowptr, colidx, rvals, n_rows, n_cols, k,
+              int(bool(exclude_self)), idx, sim, _lib.workspace("sparse_cosine_topk", nb, sp.device), nb)
+    return idx.long(), sim
+
+
+def knn_edge_index_sparse(mat, k: int, exclude_self: bool = True, device=None) -> torch.Tensor:
+    """The structural kNN graph as an ``edge_index`` [2, E] for the conv layers, as ``toolbox.knn_edge_index`` builds
+    it: source = neighbour, target = node, targets ascending, a node's in-edges in similarity order, pads dropped."""
+    idx, _ = knn_graph_sparse(mat, k, exclude_self, device)
+    dst = torch.arange(idx.size(0), device=idx.device).repeat_interleave(idx.size(1))
+    src = idx.reshape(-1)
+    keep = src >= 0
+    return torch.stack([src[keep], dst[keep]])
+
+
 def _hist_scan(sp, edges, bins, diagonal):
     colptr, rowidx, vals, rowptr, colidx, rvals = sp.layouts
     n_rows, n_cols = sp.shape

@@ -13,7 +13,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from .sparse_cosine import cosine_similarity_sparse_csr, node_similarity_sparse_histogram, sparse_columns  # noqa: F401 (sparse S at any N)
+from .sparse_cosine import cosine_similarity_sparse_csr, knn_edge_index_sparse, knn_graph_sparse, node_similarity_sparse_histogram, sparse_columns  # noqa: F401 (sparse S at any N)
 
 
 def _x(x: torch.Tensor) -> torch.Tensor:

@@ -5,7 +5,11 @@
 columns against the densifying path (`cosine_similarity_sparse`, and `torch.histc` of it) - with scipy's `c.T * c`
 on the host beside each.  The input is prepared once (`sparse_columns`; its time is listed apart).  Wall-clock
 medians around a device synchronisation - the CSR route reads nnz on the host, so it is timed as a caller sees it -
-after a warm-up and a preheat; one JSON line per matrix (profiles/sparse_cosine.txt)."""
+after a warm-up and a preheat; one JSON line per matrix (profiles/sparse_cosine.txt).
+
+`--topk K`: instead, on the same three matrices, the structural kNN graph (`knn_graph_sparse`, k = K) against what
+there was before it - the CSR product followed by a torch per-row top-k of its rows - three runs each, interleaved,
+every run's wall clock listed (profiles/sparse_cosine_topk.txt)."""
 import argparse
 import json
 import os
@@ -89,11 +93,60 @@ def measure(label, adj, reps, dense, host):
     print(json.dumps(res), flush=True)
 
 
+def csr_then_torch_topk(sp, k):
+    """What a caller had before `knn_graph_sparse`: all of S as a CSR tensor, then its rows ranked in torch - the
+    entries without the diagonal sorted by (row, value descending, column ascending) with stable sorts, the first k of
+    every row scattered into [cols, k]."""
+    csr = T.cosine_similarity_sparse_csr(sp)
+    n = csr.shape[0]
+    crow, col, val = csr.crow_indices().long(), csr.col_indices().long(), csr.values()
+    row = torch.repeat_interleave(torch.arange(n, device=dev), crow[1:] - crow[:-1])
+    keep = row != col
+    row, col, val = row[keep], col[keep], val[keep]
+    order = torch.argsort(val, descending=True, stable=True)          # (columns ascend inside a row already)
+    order = order[torch.argsort(row[order], stable=True)]
+    row, col, val = row[order], col[order], val[order]
+    first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    first[1:] = torch.cumsum(torch.bincount(row, minlength=n), 0)
+    rank = torch.arange(row.numel(), device=dev) - first[row]
+    keep = rank < k
+    idx = torch.full((n, k), -1, dtype=torch.int64, device=dev)
+    sim = torch.zeros((n, k), dtype=torch.float32, device=dev)
+    idx[row[keep], rank[keep]] = col[keep]
+    sim[row[keep], rank[keep]] = val[keep]
+    return idx, sim
+
+
+def measure_topk(label, adj, k, runs):
+    """The structural kNN graph (`knn_graph_sparse`, one launch) against the CSR product followed by a torch per-row
+    top-k, interleaved run by run in one session; both arms' results are compared once, before the clock starts."""
+    res = {"tool": "bench_sparse_cosine", "case": "topk", "matrix": label, "cols": int(adj.shape[1]), "nnz_M": int(adj.nnz),
+           "k": k, "runs": runs}
+    sp = T.sparse_columns(adj, device=dev)
+    got, want = T.knn_graph_sparse(sp, k), csr_then_torch_topk(sp, k)
+    res["arms_agree"] = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
+    del got, want
+    preheat(300.0)
+    fused, alt = [], []
+    for _ in range(runs):
+        fused.append(timed(lambda: T.knn_graph_sparse(sp, k), 1, warmup=0))
+        alt.append(timed(lambda: csr_then_torch_topk(sp, k), 1, warmup=0))
+    res["knn_graph_sparse_ms"], res["csr_then_torch_topk_ms"] = fused, alt
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-host", action="store_true", help="skip scipy's product")
+    ap.add_argument("--topk", type=int, default=0, metavar="K",
+                    help="time knn_graph_sparse(k=K) against CSR + torch top-k instead (three interleaved runs each)")
     args = ap.parse_args()
+    if args.topk:
+        measure_topk("config4_169343", adjacency("arxiv"), args.topk, 3)
+        measure_topk("band_300000", adjacency("band300k"), args.topk, 3)
+        measure_topk("config4_scaled_20000", adjacency("arxiv", scale=20000 / 169343), args.topk, 3)
+        return
     measure("config4_169343", adjacency("arxiv"), args.reps, False, not args.no_host)
     measure("band_300000", adjacency("band300k"), args.reps, False, not args.no_host)
     measure("config4_scaled_20000", adjacency("arxiv", scale=20000 / 169343), args.reps, True, not args.no_host)
