@@ -308,7 +308,7 @@ int sngnn_agg_forward_rows(const sngnn_graph_t *g, const float *n, const float *
  * node-centric whatever the graph;
  * knob 4 = which items the hinted node-centric backward runs (bit 0 wave-per-node, bit 1 fused;
  * default 3 - anything else leaves grad_h incomplete: timing only);
- * knob 5 = sngnn_linear_forward*, sngnn_cosine_dense, sngnn_knn_graph: 0 (default) = products on the bf16 matrix
+ * knob 5 = sngnn_linear_forward*, sngnn_cosine_dense, sngnn_knn_graph, sngnn_knn_query: 0 (default) = products on the bf16 matrix
  * cores after an exact three-way split of both operands (fp32 accumulation, an fp32 contraction's
  * rounding), 1 = fp32 MFMAs;
  * knobs 6, 7, 8 = the kNN builder's route, the dense cosine's contraction split, the in-degree below which a wave row
@@ -1372,6 +1372,25 @@ int sngnn_sparse_cosine_topk(const int64_t *colptr, const int32_t *rowidx, const
  */
 int64_t sngnn_knn_workspace_bytes(int64_t N, int k);
 int sngnn_knn_graph(const float *x, int64_t N, int64_t F, int k, int exclude_self,
+                    int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
+/*
+ * The same scan with two tables: for every QUERY row i of xq [M, F] the k rows j of the BASE xb [N, F] of largest
+ * cosine <xq_i, xb_j> / (max(|xq_i|, eps) max(|xb_j|, eps)) - a rank's node range against all N nodes, held-out
+ * nodes against a fixed base, the lists of some rows only.  Always the fused scan (no M x N matrix, no allocation,
+ * only enqueues: capturable); engine variant by sngnn_knn_graph's rule - F, knobs 5 and 6 (3 / 4 pin the tile
+ * shape; 0, 1, 2: by the rule), the 16-byte alignment of BOTH tables - and every value formed as there, so a row
+ * range xq = xb + r0 F, self_offset = r0 returns rows [r0, r0 + M) of the fused square scan bit for bit.
+ *   nbr_idx dev i32 [M, k]   base ids in rank order (cosine desc, base id asc), -1 padded when fewer than k are eligible
+ *   nbr_sim dev f32 [M, k]   their cosines (0 padded)
+ *   self_offset >= 0         base row self_offset + i is not eligible for query i (self_offset + M <= N);
+ *               == -1        every base row is eligible
+ *   xq may point into xb; both are read-only and the outputs must not overlap them.  M == 0: nothing is launched;
+ *   N == 0: every slot is padding.  k in [1, 32], M, N < 2^31.
+ *   workspace: sngnn_knn_query_workspace_bytes(M, N, k) - both tables' inverse norms and, few query rows against many
+ *   base rows being cut into up to 320 column ranges, their partial lists (M = 128, k = 32: ~10 MB)
+ */
+int64_t sngnn_knn_query_workspace_bytes(int64_t M, int64_t N, int k);
+int sngnn_knn_query(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, int k, int64_t self_offset,
                     int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // Two consumers: knn.hip ranks the values of a tile (k_knn_mfma), cosine_hist.hip counts them
 // (k_cosine_hist).  The consumer owns the tile loop, the accumulators and the epilogue; the engine owns
 // the rows' register operands, the panels in flight and the staging + MFMA loops of one tile.
+// The rows may come from a table of their own (sngnn_knn_query: load_rows takes it, products<true> is told of it).
 //
 // FH > 0 (F == 2 FH, FH a multiple of 16, F <= 128): the wave's 32 rows never change, so their
 // MFMA operands stay in REGISTERS for the whole scan - the k order of a contraction is free,
@@ -76,8 +77,13 @@ struct CosineTiles {
     // acc += the products of rows [row0, row0 + KR) with columns [ct KC, (ct + 1) KC).  The consumer calls
     // it for ct = ct_begin, ct_begin + 1, ... ct_end - 1 in this order (FH > 0: the panels of the next
     // steps are fetched and staged ahead, across tile boundaries), every thread of the workgroup.
+    // TWO (sngnn_knn_query): the rows are rows of a table of their own, xr [M, F] - the one load_rows was given -
+    // and x [N, F] is the column table only (FH > 0 reads the rows in load_rows alone).  !TWO: one table, the
+    // trailing arguments are not read.
+    template <bool TWO = false>
     __device__ __forceinline__ void products(const float *__restrict__ x, int64_t N, int64_t F, int64_t row0, int64_t ct,
-                                             int64_t ct_begin, int64_t ct_end, float *sA, float *sB, f32x16 (&acc)[CB])
+                                             int64_t ct_begin, int64_t ct_end, float *sA, float *sB, f32x16 (&acc)[CB],
+                                             const float *__restrict__ xr = nullptr, int64_t M = 0)
     {
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
         const int half = lane >> 5, l32 = lane & 31;
@@ -210,7 +216,8 @@ struct CosineTiles {
 #pragma unroll
             for (int u = 0; u < KN_LOADS; ++u) {
                 const int64_t r_a = row0 + sr + 8 * u, r_b = col0 + sr + 8 * u;
-                ra[u] = (r_a < N && kk < F) ? x[r_a * F + kk] : 0.f;
+                if constexpr (TWO) ra[u] = (r_a < M && kk < F) ? xr[r_a * F + kk] : 0.f;
+                else ra[u] = (r_a < N && kk < F) ? x[r_a * F + kk] : 0.f;
                 rb[u] = (r_b < N && kk < F) ? x[r_b * F + kk] : 0.f;
             }
         };

@@ -86,16 +86,30 @@ __device__ __forceinline__ unsigned long long merge_row(unsigned long long *list
 }
 
 // blockIdx.y = column split: this workgroup covers column tiles [y * tiles_per_split, ...) and
-// writes its lists as KEYS to part[y][N][k] (nsplit > 1) or the final idx / sim (nsplit == 1).
+// writes its lists as KEYS to part[y][rows][k] (nsplit > 1) or the final idx / sim (nsplit == 1).
 //
 // The products of a tile come from the engine in cosine_tiles.h (FH, BF3, NWV, CB: see there); this kernel owns
 // the tile loop and the selection.
-template <int FH, bool BF3, int NWV = 4, int CB = 4>
+//
+// Two tables (RECT, sngnn_knn_query): the workgroup's rows are rows of rows.xq [M, F] with inverse norms rows.invq,
+// the column tiles walk x [N, F] with inv, column rows.self_offset + i is no neighbour of row i (-1: every column is
+// eligible; exclude_self is not read) and the lists are M rows.  One table (!RECT, sngnn_knn_graph): `rows` is
+// empty, the rows are x's, and the instantiation is the kernel it was before the second table existed.
+template <bool RECT>
+struct KnnRows { const float *xq; int64_t M; const float *invq; int64_t self_offset; };
+template <>
+struct KnnRows<false> {};
+
+template <int FH, bool BF3, int NWV = 4, int CB = 4, bool RECT = false>
 __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__ x, int64_t N, int64_t F,
                                                   const float *__restrict__ inv, int k, int exclude_self,
                                                   int tiles_per_split, unsigned long long *__restrict__ part,
-                                                  int32_t *__restrict__ out_idx, float *__restrict__ out_sim)
+                                                  int32_t *__restrict__ out_idx, float *__restrict__ out_sim,
+                                                  KnnRows<RECT> rows = {})
 {
+    const float *xq = x, *invq = inv;
+    int64_t M = N, self = -1;
+    if constexpr (RECT) { xq = rows.xq; M = rows.M; invq = rows.invq; self = rows.self_offset; }
     using Eng = CosineTiles<FH, BF3, NWV, CB>;
     constexpr int KC = Eng::KC, KR = Eng::KR;                  // columns per tile, rows per workgroup
     __shared__ float sA[Eng::SA_FLOATS];
@@ -113,8 +127,8 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
     for (int q = lane; q < 32 * KNN_MAX_K; q += 64) s_list[wave][q / KNN_MAX_K][q % KNN_MAX_K] = 0ull;
     if (lane < 32) {
         s_thr[wave][lane] = 0ull; s_thrf[wave][lane] = -INFINITY; s_pend[wave][lane] = 0;
-        s_ts[wave][lane] = (row0 + wave * 32 + lane < N) ? -INFINITY : INFINITY;      // (rows beyond N: never a candidate)
-        s_irow[wave][lane] = (row0 + wave * 32 + lane < N) ? inv[row0 + wave * 32 + lane] : 0.f;
+        s_ts[wave][lane] = (row0 + wave * 32 + lane < M) ? -INFINITY : INFINITY;      // (rows beyond M: never a candidate)
+        s_irow[wave][lane] = (row0 + wave * 32 + lane < M) ? invq[row0 + wave * 32 + lane] : 0.f;
     }
     const int cap = KNN_MAX_K - k;                               // spare slots behind a row's list
     const int64_t ncol_tiles = (N + KC - 1) / KC;
@@ -122,7 +136,7 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
     const int64_t ct_end = min(ncol_tiles, ct_begin + tiles_per_split);
 
     Eng eng;
-    eng.load_rows(x, N, F, row0);
+    eng.load_rows(xq, M, F, row0);
 
     for (int64_t ct = ct_begin; ct < ct_end; ++ct) {
         const int64_t col0 = ct * KC;
@@ -141,7 +155,7 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
         }
 #pragma unroll
         for (int b = 0; b < CB; ++b) icol[b] = jcol[b] < N ? icol[b] : 0.f;
-        eng.products(x, N, F, row0, ct, ct_begin, ct_end, sA, sB, acc);
+        eng.template products<RECT>(x, N, F, row0, ct, ct_begin, ct_end, sA, sB, acc, xq, M);
 #if defined(SNGNN_KNN_EXP) && SNGNN_KNN_EXP == 1        // timing experiment: no selection at all
 #pragma unroll
         for (int b = 0; b < CB; ++b)
@@ -214,7 +228,8 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
             bool any = false;
 #pragma unroll
             for (int b = 0; b < CB; ++b) {
-                const bool ok = i < N && jcol[b] < N && !(exclude_self && jcol[b] == i);
+                const bool ok = i < M && jcol[b] < N &&
+                                !(RECT ? (self >= 0 && jcol[b] == i + self) : (exclude_self && jcol[b] == i));
                 key[b] = ok ? sel_key(sv[b], (unsigned)jcol[b]) : 0ull;
                 if (key[b] <= thr) key[b] = 0ull;                        // cannot enter the list
                 any |= key[b] != 0ull;
@@ -294,7 +309,7 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
                     const unsigned u = (unsigned)(T >> 32);
                     const float tf = T ? __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u) : -INFINITY;
                     s_thrf[wave][rowh] = tf;
-                    // (rows beyond N never get here: their lists take no key)
+                    // (rows beyond M never get here: their lists take no key)
                     const float tq = tf / s_irow[wave][rowh];
                     s_ts[wave][rowh] = tq - (fabsf(tq) * 1e-6f + 1e-30f);
                 }
@@ -316,10 +331,10 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
     wave_lds_sync();
     for (int lr = 0; lr < 32; ++lr) {
         const int64_t i = row0 + wave * 32 + lr;
-        if (i >= N) break;
+        if (i >= M) break;
         const unsigned long long *list = s_list[wave][lr];
         if (part != nullptr) {
-            if (lane < k) part[((size_t)blockIdx.y * N + i) * k + lane] = list[lane];
+            if (lane < k) part[((size_t)blockIdx.y * M + i) * k + lane] = list[lane];
             continue;
         }
         if (lane < k) {
@@ -343,7 +358,7 @@ __global__ __launch_bounds__(64 * NWV) void k_knn_mfma(const float *__restrict__
     }
 }
 
-// top-k of the column splits' lists of one row (nsplit * k keys, 128 at a time)
+// top-k of the column splits' lists of one row (nsplit * k keys, 128 at a time); N = the rows of the lists
 __global__ __launch_bounds__(256) void k_knn_merge(const unsigned long long *__restrict__ part, int64_t N,
                                                    int k, int nsplit, int32_t *__restrict__ out_idx,
                                                    float *__restrict__ out_sim)
@@ -580,6 +595,80 @@ extern "C" int sngnn_knn_graph(const float *x, int64_t N, int64_t F, int k, int 
     else if (areg && F == 32) { if (bf3) k_knn_mfma<16, true><<<grid, 256, 0, st>>>(x, N, F, inv, k, exclude_self, tps, pp, nbr_idx, nbr_sim); else k_knn_mfma<16, false><<<grid, 256, 0, st>>>(x, N, F, inv, k, exclude_self, tps, pp, nbr_idx, nbr_sim); }
     else k_knn_mfma<0, false><<<grid, 256, 0, st>>>(x, N, F, inv, k, exclude_self, tps, pp, nbr_idx, nbr_sim);
     if (ns_used > 1) k_knn_merge<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(part, N, k, ns_used, nbr_idx, nbr_sim);
+    SN_HIP(hipGetLastError());
+    return SNGNN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Two tables: the lists of M query rows against a base of N rows (see knn_scan).  The engine variant follows the
+// square scan's rule - F, knob 5, and the 16-byte alignment of BOTH tables, so that a row range of an aligned base
+// takes the variant the square scan takes on that base.  The column splits are sized for occupancy from the base's
+// tile count - few row blocks against many column tiles is the common case here, and a cap at the number of row
+// blocks (knn_splits: the square scan never has more column tiles than 2 x row blocks) would leave one 128-row
+// query block on one CU.
+// ---------------------------------------------------------------------------
+struct KnnQueryPlan { int64_t nrb, nct; int tps, ns; };
+static KnnQueryPlan knn_query_plan(int64_t M, int64_t N, int rows_wg, int cols_tile)
+{
+    KnnQueryPlan p;
+    p.nrb = (M + rows_wg - 1) / rows_wg;
+    p.nct = (N + cols_tile - 1) / cols_tile;
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>(p.nct, (320 + p.nrb - 1) / std::max<int64_t>(p.nrb, 1)));
+    p.tps = (int)((p.nct + want - 1) / std::max<int64_t>(want, 1));          // column tiles per split
+    p.ns = p.tps > 0 ? (int)((p.nct + p.tps - 1) / p.tps) : 0;              // splits in use (<= want <= 320)
+    return p;
+}
+
+extern "C" int64_t sngnn_knn_query_workspace_bytes(int64_t M, int64_t N, int k)
+{
+    if (M < 0 || N < 0 || k < 1) return 0;
+    const int ns = std::max(knn_query_plan(M, N, KN_M, KN_M).ns, knn_query_plan(M, N, 256, 64).ns);       // (either tile shape)
+    // the inverse norms of the queries and of the base, then the column splits' partial lists
+    return (M + 63) / 64 * 256 + (N + 63) / 64 * 256 + (ns > 1 ? (int64_t)ns * M * k * 8 : 0) + 256;
+}
+
+extern "C" int sngnn_knn_query(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, int k,
+                               int64_t self_offset, int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream)
+{
+    SN_REQUIRE(M >= 0 && N >= 0 && F >= 1, SNGNN_EINVAL, "bad shape");
+    SN_REQUIRE(k >= 1 && k <= KNN_MAX_K, SNGNN_EINVAL, "k must be in [1, " + std::to_string(KNN_MAX_K) + "]");
+    SN_REQUIRE(M < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), SNGNN_EINVAL, "too many rows");
+    SN_REQUIRE(self_offset >= -1 && (self_offset < 0 || self_offset + M <= N), SNGNN_EINVAL,
+               "self_offset: the queries are not rows [self_offset, self_offset + M) of the base");
+    if (M == 0) return SNGNN_OK;
+    SN_REQUIRE(xq && nbr_idx && nbr_sim && workspace && (xb || N == 0), SNGNN_EINVAL, "NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {                              // no base row: every slot is padding (a merge of no lists)
+        k_knn_merge<<<(unsigned)((M + 3) / 4), 256, 0, st>>>(nullptr, M, k, 0, nbr_idx, nbr_sim);
+        SN_HIP(hipGetLastError());
+        return SNGNN_OK;
+    }
+    float *invq = (float *)workspace;
+    float *invb = (float *)((char *)workspace + (M + 63) / 64 * 256);
+    unsigned long long *part = (unsigned long long *)((char *)invb + (N + 63) / 64 * 256);
+    const bool areg = (uintptr_t)xq % 16 == 0 && (uintptr_t)xb % 16 == 0;
+    const bool wide = areg && knn_wide(F, xb);
+    const KnnQueryPlan p = knn_query_plan(M, N, wide ? 256 : KN_M, wide ? 64 : KN_M);
+    k_knn_inv_norm<<<(unsigned)((M + 3) / 4), 256, 0, st>>>(xq, M, F, invq);
+    k_knn_inv_norm<<<(unsigned)((N + 3) / 4), 256, 0, st>>>(xb, N, F, invb);
+    dim3 grid((unsigned)p.nrb, (unsigned)p.ns);
+    unsigned long long *pp = p.ns > 1 ? part : nullptr;
+    const bool bf3 = !sngnn::fp32_mfma_only();          // sngnn_tuning_set(5, 1): fp32 MFMAs
+    const KnnRows<true> rows = {xq, M, invq, self_offset};
+#define SN_KNNQ_GO(FH_, BF3_, NWV_, CB_)                                                                           \
+    k_knn_mfma<FH_, BF3_, NWV_, CB_, true><<<grid, 64 * NWV_, 0, st>>>(xb, N, F, invb, k, 0, p.tps, pp, nbr_idx,     \
+                                                                       nbr_sim, rows)
+    if (wide && F == 128) SN_KNNQ_GO(64, true, 8, 2);
+    else if (wide && F == 96) SN_KNNQ_GO(48, true, 8, 2);
+    else if (wide && F == 64) SN_KNNQ_GO(32, true, 8, 2);
+    else if (wide) SN_KNNQ_GO(16, true, 8, 2);
+    else if (areg && F == 128) { if (bf3) SN_KNNQ_GO(64, true, 4, 4); else SN_KNNQ_GO(64, false, 4, 4); }
+    else if (areg && F == 96) { if (bf3) SN_KNNQ_GO(48, true, 4, 4); else SN_KNNQ_GO(48, false, 4, 4); }
+    else if (areg && F == 64) { if (bf3) SN_KNNQ_GO(32, true, 4, 4); else SN_KNNQ_GO(32, false, 4, 4); }
+    else if (areg && F == 32) { if (bf3) SN_KNNQ_GO(16, true, 4, 4); else SN_KNNQ_GO(16, false, 4, 4); }
+    else SN_KNNQ_GO(0, false, 4, 4);
+#undef SN_KNNQ_GO
+    if (p.ns > 1) k_knn_merge<<<(unsigned)((M + 3) / 4), 256, 0, st>>>(part, M, k, p.ns, nbr_idx, nbr_sim);
     SN_HIP(hipGetLastError());
     return SNGNN_OK;
 }

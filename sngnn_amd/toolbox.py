@@ -13,6 +13,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
+from .knn_query import knn_edge_index_partitioned, knn_edge_index_rows, knn_graph_partitioned, knn_graph_rows, knn_query  # noqa: F401 (a row range / query set against a base)
 from .sparse_cosine import cosine_similarity_sparse_csr, knn_edge_index_sparse, knn_graph_sparse, node_similarity_sparse_histogram, sparse_columns  # noqa: F401 (sparse S at any N)
 
 
