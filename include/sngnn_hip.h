@@ -1392,6 +1392,35 @@ int sngnn_knn_graph(const float *x, int64_t N, int64_t F, int k, int exclude_sel
 int64_t sngnn_knn_query_workspace_bytes(int64_t M, int64_t N, int k);
 int sngnn_knn_query(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, int k, int64_t self_offset,
                     int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
+/*
+ * The cosine scans straight from an fp16 / bf16 table (2 F bytes a row, read as stored - no fp32 copy): the kNN graph,
+ * the two-table query and the histogram above on the tile engine's half forms.  A value of such a table has two
+ * (fp16) resp. one (bf16) of the three bf16 planes the fp32 scan splits a float into; the planes it has are used as
+ * they are and only their products are issued - 4 resp. 1 of the 8 matrix instructions per product - in the fp32
+ * scan's order.  Inverse norms, selection, counting and statistics are the fp32 entries'.  On a table of finite
+ * values the outputs are those of the fp32 fused scan on the widened table, bit for bit (the planes left out are
+ * exactly +0.0 there; csrc/cosine_tiles.h).  A non-finite entry is outside that statement.
+ *   dtype   SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16, the type of every table of the call (anything else: SNGNN_EINVAL
+ *           with "dtype" in sngnn_last_error(), before any pointer is looked at)
+ *   sngnn_cosine_scan_half_supported   1 iff the native scan exists for the knobs as they stand: dtype as above, F in
+ *           {32, 64, 96, 128}, knob 5 off (bf16 products) and knob 6 not 3 (the half forms have the 256 x 64 tile only)
+ *   sngnn_knn_graph_route              1: sngnn_knn_graph would run the fused scan on N rows (knob 6 as it stands),
+ *           2: it would materialise S and select.  sngnn_knn_graph_half ALWAYS runs the fused scan; a caller that
+ *           wants the fp32 call's route on small tables asks here first.
+ * Refused with SNGNN_EINVAL, nothing launched: what sngnn_cosine_scan_half_supported refuses, a table whose base is
+ * not 16-byte aligned, and whatever the fp32 entry refuses (k, shapes, NULL, self_offset).  The empty shapes behave
+ * as in the fp32 entries.  Only enqueue on `stream`.
+ *   workspace: sngnn_knn_workspace_bytes(N, k) / sngnn_knn_query_workspace_bytes(M, N, k) /
+ *              sngnn_cosine_hist_workspace_bytes(N, F, bins, groups) - the fp32 entries' sizes
+ */
+int sngnn_cosine_scan_half_supported(int64_t F, int dtype);
+int sngnn_knn_graph_route(int64_t N);
+int sngnn_knn_graph_half(const void *x, int dtype, int64_t N, int64_t F, int k, int exclude_self,
+                         int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
+int sngnn_knn_query_half(const void *xq, int64_t M, const void *xb, int dtype, int64_t N, int64_t F, int k,
+                         int64_t self_offset, int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
+int sngnn_cosine_hist_half(const void *x, int dtype, int64_t N, int64_t F, const int32_t *y, const float *edges,
+                           int bins, unsigned long long *counts, double *stats, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------
  * R replicas of one 1-layer model trained together (sngnn_amd/splits.py): the sweep scripts'

@@ -76,8 +76,8 @@ SIGNATURES = {
     "sngnn_bn_train_backward": (_i32, [_vp, _vp, _vp, _i64, _i32] + [_vp] * 4 + [_f32, _vp, _f32] + [_vp] * 6),
     "sngnn_bn_post_forward": (_i32, [_vp, _i64, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _f32, _vp, _f32] + [_vp] * 5),
     "sngnn_bn_post_backward": (_i32, [_vp, _vp, _i64, _i32] + [_vp] * 5 + [_f32, _vp, _f32] + [_vp] * 5),
-    "sngnn_knn_workspace_bytes": (_i64, [_i64, _i32]), "sngnn_knn_query_workspace_bytes": (_i64, [_i64, _i64, _i32]),
-    "sngnn_knn_graph": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]), "sngnn_knn_query": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "sngnn_knn_workspace_bytes": (_i64, [_i64, _i32]), "sngnn_knn_query_workspace_bytes": (_i64, [_i64, _i64, _i32]), "sngnn_knn_graph_route": (_i32, [_i64]),
+    "sngnn_knn_graph": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]), "sngnn_knn_query": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]), "sngnn_knn_graph_half": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]), "sngnn_knn_query_half": (_i32, [_vp, _i64, _vp, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "sngnn_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_scatter_sum_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_weighted_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
@@ -131,7 +131,7 @@ SIGNATURES = {
     "sngnn_cosine_dense": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "sngnn_cosine_class_sums": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_cosine_hist_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
-    "sngnn_cosine_hist": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "sngnn_cosine_hist": (_i32, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]), "sngnn_cosine_scan_half_supported": (_i32, [_i64, _i32]), "sngnn_cosine_hist_half": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "sngnn_edge_cosine": (_i32, [_vp, _i64, _i64, _vp, _i64, _vp, _vp]), "sngnn_segment_mean": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "sngnn_sparse_pair_dot": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "sngnn_sparse_cosine_count_workspace_bytes": (_i64, [_i64, _i64]), "sngnn_sparse_cosine_fill_workspace_bytes": (_i64, [_i64, _i64]),

@@ -55,6 +55,8 @@ int set_bwd_mode(int v);      // agg_bwd.hip (sngnn_tuning_set knobs 3, 4)
 int set_bwd_roles(int v);
 int set_lin_mode(int v);       // linear.hip (knob 5)
 int set_knn_route(int v);      // knn.hip (knob 6)
+bool knn_no_wide_tiles();      // knn.hip: knob 6 == 3 (the fused scan stays on 128 x 128 tiles)
+int hist_copies_knob();        // cosine_hist.hip: knob 10 as it stands
 int set_cosine_split(int v);   // toolbox.hip (knob 7)
 int set_hist_copies(int v);    // cosine_hist.hip (knob 10)
 bool fp32_mfma_only();         // knob 5 == 1: the fp32 contractions stay on fp32 MFMAs

@@ -1,7 +1,8 @@
 // The tile engine of the fused cosine scans (gfx950): raw products X_rows X_cols^T of one workgroup's
 // row block against one column tile after another, on the matrix cores at fp32 rounding, never stored.
-// Two consumers: knn.hip ranks the values of a tile (k_knn_mfma), cosine_hist.hip counts them
-// (k_cosine_hist).  The consumer owns the tile loop, the accumulators and the epilogue; the engine owns
+// Two consumers: knn_scan.h ranks the values of a tile (k_knn_mfma), cosine_hist_scan.h counts them
+// (k_cosine_hist); knn.hip / cosine_hist.hip launch them on fp32 tables, knn_half.hip / cosine_hist_half.hip on
+// fp16 / bf16 tables.  The consumer owns the tile loop, the accumulators and the epilogue; the engine owns
 // the rows' register operands, the panels in flight and the staging + MFMA loops of one tile.
 // The rows may come from a table of their own (sngnn_knn_query: load_rows takes it, products<true> is told of it).
 //
@@ -24,6 +25,8 @@
 // Result layout (C/D of a 32 x 32 block): acc[b][r] of lane l is column 32 b + (l & 31), row
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5) of the wave's 32 rows.
 #pragma once
+#include <type_traits>
+
 #include "device_utils.h"
 
 namespace sngnn {
@@ -33,28 +36,57 @@ constexpr int KN_M = 128, KN_K = 32, KN_LD = KN_K + 4, KN_LOADS = KN_M * KN_K / 
 typedef float knn_f4 __attribute__((ext_vector_type(4)));
 constexpr int KN_PS = 80;                      // bytes per row of a bf16 plane of the column panel
 
-template <int FH, bool BF3, int NWV = 4, int CB = 4>
+// PL = the bf16 planes a stored value has, i.e. the table's storage type: 3 = fp32 (the forms above), 2 = fp16
+// (11 significant bits: plane 3 of the widened value is +0.0), 1 = bf16 (the stored 16 bits ARE plane 1).  PL < 3
+// exists for the <8, 2> register-operand shape only.  The table is `const XT *`, 2 F bytes a row; the planes that
+// are kept are the bits the fp32 form computes from the widened table, the products that are issued are the fp32
+// form's products of those planes in its order, and the planes and products that are left out are the ones whose
+// operands are all +0.0 there (the contract this rests on).
+template <int FH, bool BF3, int NWV = 4, int CB = 4, int PL = 3>
 struct CosineTiles {
     static_assert(!BF3 || FH > 0, "the bf16 form is the register-operand path's");
     static_assert((NWV == 4 && CB == 4) || (BF3 && FH > 0), "other tile shapes: the bf16 register-operand path only");
     static_assert((4 * CB) % NWV == 0 && 4 * CB / NWV >= 1 && 4 * CB / NWV <= 4, "staging: 1..4 vectors per thread and step");
+    static_assert(PL == 3 || ((PL == 1 || PL == 2) && BF3 && FH > 0 && NWV == 8 && CB == 2), "half tables: the <8, 2> register-operand shape only");
     static constexpr int KR = 32 * NWV, KC = 32 * CB;                  // rows per workgroup, columns per tile
+    using XT = std::conditional_t<PL == 3, float, unsigned short>;     // one stored value
     // floats of the two LDS panels the consumer declares (__shared__, sB aligned to 16 bytes)
     static constexpr int SA_FLOATS = FH > 0 ? 1 : KN_M * KN_LD;
-    static constexpr int SB_FLOATS = (FH > 0 ? 2 : 1) * (BF3 ? 3 * KC * KN_PS / 4 : KC * KN_LD);   // FH > 0: two buffers
+    static constexpr int SB_FLOATS = (FH > 0 ? 2 : 1) * (BF3 ? PL * KC * KN_PS / 4 : KC * KN_LD);   // FH > 0: two buffers
 
     float areg[(FH > 0 && !BF3) ? FH : 1];
-    sn_u32x4 ap1[BF3 ? FH / 8 : 1], ap2[BF3 ? FH / 8 : 1], ap3[BF3 ? FH / 8 : 1];     // the rows' three bf16 planes
+    sn_u32x4 ap1[BF3 ? FH / 8 : 1], ap2[BF3 && PL >= 2 ? FH / 8 : 1], ap3[BF3 && PL == 3 ? FH / 8 : 1];     // the rows' bf16 planes
     knn_f4 rb0, rb1, rb2, rb3;                                                       // the column panel in flight (FH > 0)
+    sn_u32x4 rh;                                                                     // ... of a half table: 8 k-slots as stored
+
+    // 8 stored fp16 values -> planes 1 and 2 of their (exact) fp32 values
+    static __device__ __forceinline__ void split_f16x8(const sn_u32x4 &h, sn_u32x4 &p1, sn_u32x4 &p2)
+    {
+        float av[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            av[2 * i] = Half16<__half>::widen((unsigned short)(h[i] & 0xFFFFu));
+            av[2 * i + 1] = Half16<__half>::widen((unsigned short)(h[i] >> 16));
+        }
+        sn_u32x4 p3;                                                      // +0.0 in every slot: not kept
+        split_bf16x8(av, p1, p2, p3);
+    }
 
     // once per workgroup, before the first tile: the wave's rows into registers (FH > 0)
-    __device__ __forceinline__ void load_rows(const float *__restrict__ x, int64_t N, int64_t F, int64_t row0)
+    __device__ __forceinline__ void load_rows(const XT *__restrict__ x, int64_t N, int64_t F, int64_t row0)
     {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int half = lane >> 5, l32 = lane & 31;
         if constexpr (FH > 0) {
             const int64_t ar = min(row0 + wave * 32 + l32, N - 1);          // (rows >= N are never used)
-            if constexpr (!BF3) {
+            if constexpr (PL < 3) {
+#pragma unroll
+                for (int q = 0; q < FH / 8; ++q) {
+                    const sn_u32x4 h = *reinterpret_cast<const sn_u32x4 *>(x + ar * F + half * FH + 8 * q);
+                    if constexpr (PL == 1) ap1[q] = h;
+                    else split_f16x8(h, ap1[q], ap2[q]);
+                }
+            } else if constexpr (!BF3) {
 #pragma unroll
                 for (int q = 0; q < FH / 4; ++q) {
                     const float4 v = *reinterpret_cast<const float4 *>(x + ar * F + half * FH + 4 * q);
@@ -72,6 +104,8 @@ struct CosineTiles {
         }
         const knn_f4 z = {0.f, 0.f, 0.f, 0.f};
         rb0 = z; rb1 = z; rb2 = z; rb3 = z;
+        const sn_u32x4 zh = {0u, 0u, 0u, 0u};
+        rh = zh;
     }
 
     // acc += the products of rows [row0, row0 + KR) with columns [ct KC, (ct + 1) KC).  The consumer calls
@@ -81,9 +115,9 @@ struct CosineTiles {
     // and x [N, F] is the column table only (FH > 0 reads the rows in load_rows alone).  !TWO: one table, the
     // trailing arguments are not read.
     template <bool TWO = false>
-    __device__ __forceinline__ void products(const float *__restrict__ x, int64_t N, int64_t F, int64_t row0, int64_t ct,
+    __device__ __forceinline__ void products(const XT *__restrict__ x, int64_t N, int64_t F, int64_t row0, int64_t ct,
                                              int64_t ct_begin, int64_t ct_end, float *sA, float *sB, f32x16 (&acc)[CB],
-                                             const float *__restrict__ xr = nullptr, int64_t M = 0)
+                                             const XT *__restrict__ xr = nullptr, int64_t M = 0)
     {
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
         const int half = lane >> 5, l32 = lane & 31;
@@ -107,15 +141,22 @@ struct CosineTiles {
             // Staging map: 16 consecutive lanes write rows r and r + 4 (not r and r + 1): with the 80-byte
             // plane rows their 8-byte stores cover all 32 banks once - adjacent rows overlapped in four
             // (SQ_LDS_BANK_CONFLICT 777 M cycles at arxiv size, 1.24 per LDS instruction, all from these stores).
-            const int seg = tid & 7, slot = tid >> 3;
+            // A half table (PL < 3): a step's panel is KC rows of 4 vectors of 8 k-slots (two of each half) - 256
+            // vectors, one for each thread of the first four waves; the others stage nothing.  Thread t owns vector
+            // (t & 3) of row slot (t >> 2), the same row permutation: 8 consecutive lanes write rows r and r + 4, 16
+            // bytes each, and cover the 32 banks once.
+            const int seg = PL < 3 ? tid & 3 : tid & 7, slot = PL < 3 ? tid >> 2 : tid >> 3;
             const int pr = (slot & ~7) | ((slot & 7) >> 1) | ((slot & 1) << 2);
-            const int kseg = seg < 4 ? 4 * seg : FH + 4 * (seg - 4);
+            const int kseg = PL < 3 ? (seg < 2 ? 8 * seg : FH + 8 * (seg - 2)) : (seg < 4 ? 4 * seg : FH + 4 * (seg - 4));
+            const bool stager = PL == 3 || slot < KC;                     // (wave-uniform)
             constexpr int NS = FH / 16;                                   // steps per tile
-            constexpr int PANEL = BF3 ? 3 * KC * KN_PS : KC * KN_LD * 4;     // bytes of one buffer
+            constexpr int PANEL = BF3 ? PL * KC * KN_PS : KC * KN_LD * 4;    // bytes of one buffer
             constexpr int SROWS = 8 * NWV, UV = KC / SROWS;               // rows staged per vector slot, vectors per thread
 #define SN_KNN_FETCH(COL0, S0)                                                                            \
-            {                                                                                             \
-                const float *g_ = x + (S0) + kseg;                                                        \
+            if constexpr (PL < 3) {                                                                       \
+                if (stager) rh = *(const sn_u32x4 *)(x + (S0) + kseg + min((COL0) + pr, N - 1) * F);      \
+            } else {                                                                                      \
+                const XT *g_ = x + (S0) + kseg;                                                           \
                 rb0 = *(const knn_f4 *)(g_ + min((COL0) + pr, N - 1) * F);                                \
                 if constexpr (UV > 1) rb1 = *(const knn_f4 *)(g_ + min((COL0) + pr + SROWS, N - 1) * F);  \
                 if constexpr (UV > 2) rb2 = *(const knn_f4 *)(g_ + min((COL0) + pr + 2 * SROWS, N - 1) * F); \
@@ -125,7 +166,19 @@ struct CosineTiles {
             // BF3: plane p of column row r at byte (p * KN_M + r) * KN_PS; its 32 k-slots are the
             // step's 16 of half 0 followed by the 16 of half 1 (seg 0..3 | 4..7, 8 bytes each)
             auto stage = [&](int boff) {
-                if constexpr (!BF3) {
+                if constexpr (PL < 3) {
+                    // the vector's 8 k-slots are 16 bytes of the plane row as they stand (bf16), or widened and split
+                    if (stager) {
+                        unsigned char *wbh = sBb + boff + pr * KN_PS + 16 * seg;
+                        if constexpr (PL == 1) *(sn_u32x4 *)(wbh) = rh;
+                        else {
+                            sn_u32x4 p1, p2;
+                            split_f16x8(rh, p1, p2);
+                            *(sn_u32x4 *)(wbh) = p1;
+                            *(sn_u32x4 *)(wbh + KC * KN_PS) = p2;
+                        }
+                    }
+                } else if constexpr (!BF3) {
                     float *wb = reinterpret_cast<float *>(sBb + boff) + pr * KN_LD + 4 * seg;
                     *(knn_f4 *)(wb) = rb0;
                     if constexpr (UV > 1) *(knn_f4 *)(wb + SROWS * KN_LD) = rb1;
@@ -152,7 +205,7 @@ struct CosineTiles {
             auto fetch_step = [&](int64_t L) {
                 const int64_t t_ = ct_begin + L / NS;
                 const int st_ = (int)(L % NS) * 16;
-                if (t_ < ct_end) SN_KNN_FETCH(t_ * KC, st_)
+                if (t_ < ct_end) { SN_KNN_FETCH(t_ * KC, st_) }
             };
             if (ct == ct_begin) {
                 fetch_step(0);
@@ -177,8 +230,8 @@ struct CosineTiles {
                         for (int b = 0; b < CB; ++b) {
                             const unsigned char *r_ = pb3 + 32 * b * KN_PS + 16 * g;
                             const sn_u32x4 b1 = *(const sn_u32x4 *)(r_);
-                            const sn_u32x4 b2 = *(const sn_u32x4 *)(r_ + KC * KN_PS);
-                            const sn_u32x4 b3 = *(const sn_u32x4 *)(r_ + 2 * KC * KN_PS);
+                            const sn_u32x4 b2 = *(const sn_u32x4 *)(r_ + (PL >= 2 ? KC * KN_PS : 0));          // (PL planes exist)
+                            const sn_u32x4 b3 = *(const sn_u32x4 *)(r_ + (PL == 3 ? 2 * KC * KN_PS : 0));
 #if defined(SNGNN_KNN_EXP) && SNGNN_KNN_EXP == 2        // timing experiment: one product of eight
 #define SN_KNN_M3(PA, PB) asm volatile("" ::"v"(PA), "v"(PB));
                             acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sn_bf16x8, ap1[aq]),
@@ -188,8 +241,16 @@ struct CosineTiles {
                             acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sn_bf16x8, PA), \
                                                                              __builtin_bit_cast(sn_bf16x8, PB), acc[b], 0, 0, 0);
 #endif
+                            // (row plane, column plane): (3,2)(2,3)(3,1)(2,2)(1,3)(2,1)(1,2)(1,1) - of these, the ones
+                            // whose planes the table has, in this order
+                            if constexpr (PL == 3) {
                             SN_KNN_M3(ap3[aq], b2) SN_KNN_M3(ap2[aq], b3) SN_KNN_M3(ap3[aq], b1) SN_KNN_M3(ap2[aq], b2)
                             SN_KNN_M3(ap1[aq], b3) SN_KNN_M3(ap2[aq], b1) SN_KNN_M3(ap1[aq], b2) SN_KNN_M3(ap1[aq], b1)
+                            } else if constexpr (PL == 2) {
+                            SN_KNN_M3(ap2[aq], b2) SN_KNN_M3(ap2[aq], b1) SN_KNN_M3(ap1[aq], b2) SN_KNN_M3(ap1[aq], b1)
+                            } else {
+                            SN_KNN_M3(ap1[aq], b1)
+                            }
 #undef SN_KNN_M3
                         }
                     }
@@ -257,6 +318,26 @@ static __global__ __launch_bounds__(256) void k_knn_inv_norm(const float *__rest
     const float *p = x + row * F;
     float ss = 0.f;
     for (int64_t c = lane; c < F; c += 64) ss = fmaf(p[c], p[c], ss);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    if (lane == 0) inv[row] = 1.0f / fmaxf(sqrtf(ss), EPS_NORM);
+}
+
+// the same of a half table (S = __half or __hip_bfloat16): every value widened, then the lane striding, the fmaf
+// chain and the shuffle tree above - the bits of k_knn_inv_norm on the widened table
+template <typename S>
+static __global__ __launch_bounds__(256) void k_knn_inv_norm_half(const unsigned short *__restrict__ x, int64_t N, int64_t F,
+                                                                  float *__restrict__ inv)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const unsigned short *p = x + row * F;
+    float ss = 0.f;
+    for (int64_t c = lane; c < F; c += 64) {
+        const float v = Half16<S>::widen(p[c]);
+        ss = fmaf(v, v, ss);
+    }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
     if (lane == 0) inv[row] = 1.0f / fmaxf(sqrtf(ss), EPS_NORM);

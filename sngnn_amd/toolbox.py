@@ -13,7 +13,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from .knn_query import knn_edge_index_partitioned, knn_edge_index_rows, knn_graph_partitioned, knn_graph_rows, knn_query  # noqa: F401 (a row range / query set against a base)
+from .knn_query import _call_cosine_hist, _call_knn_graph, _scan_tables, knn_edge_index_partitioned, knn_edge_index_rows, knn_graph_partitioned, knn_graph_rows, knn_query  # noqa: F401 (a row range / query set against a base)
 from .sparse_cosine import cosine_similarity_sparse_csr, knn_edge_index_sparse, knn_graph_sparse, node_similarity_sparse_histogram, sparse_columns  # noqa: F401 (sparse S at any N)
 
 
@@ -113,14 +113,14 @@ def _hist_edges(lo, hi, bins, device):
     return torch.linspace(lo, hi, bins + 1, dtype=torch.float64, device=device).to(torch.float32)
 
 
-def _hist_scan(x, y32, edges, bins):
+def _hist_scan(x, y32, edges, bins, code=0):
     n, f = x.shape
     lib = _lib.load()
     groups = 1 if y32 is None else 2
     counts = torch.empty((groups, bins + 2), dtype=torch.int64, device=x.device)
     stats = torch.empty(3, dtype=torch.float64, device=x.device)
     ws = _lib.workspace("cosine_hist", lib.sngnn_cosine_hist_workspace_bytes(n, f, bins, groups), x.device)
-    _lib.call("sngnn_cosine_hist", x.device, x, n, f, y32, edges, bins, counts, stats, ws)
+    _call_cosine_hist(code, x, n, f, y32, edges, bins, counts, stats, ws)
     return counts, stats
 
 
@@ -135,7 +135,7 @@ def node_similarity_histogram(x, bins: int = 200, range=(-1.0, 1.0), y=None, cla
     bin (``outside`` is then 0; a duplicate row's cosine may round to 1 + 1 ulp); ``clamp=False`` is numpy's
     behaviour: they are left out of ``counts`` and reported in ``outside``.  ``range=None`` uses the data's own
     [min, max] (one scan for them - it reads the host - and one to count).  ``mean`` equals
-    ``node_similarity_dense_large_parted(x, corrected=True)[1]``."""
+    ``node_similarity_dense_large_parted(x, corrected=True)[1]``.  An fp16 / bf16 table is scanned as stored (``_scan_tables``)."""
     bins = int(bins)
     if not 1 <= bins <= HIST_MAX_BINS:
         raise ValueError(f"bins must be in [1, {HIST_MAX_BINS}]")
@@ -143,7 +143,7 @@ def node_similarity_histogram(x, bins: int = 200, range=(-1.0, 1.0), y=None, cla
         lo, hi = float(range[0]), float(range[1])
         if not (lo < hi) or lo in (float("inf"), float("-inf")) or hi in (float("inf"), float("-inf")):
             raise ValueError("range must be (lo, hi) with finite lo < hi")
-    x = _x(x)
+    (x,), code = _scan_tables(x)
     n = x.size(0)
     y32 = None
     if y is not None:
@@ -158,14 +158,14 @@ def node_similarity_histogram(x, bins: int = 200, range=(-1.0, 1.0), y=None, cla
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("range=None reads the data's min / max on the host and cannot be captured in a "
                                "graph: pass a fixed range")
-        _, st = _hist_scan(x, None, make_edges(-1.0, 1.0), bins)
+        _, st = _hist_scan(x, None, make_edges(-1.0, 1.0), bins, code)
         lo, hi = (float(v) for v in st[:2].tolist())
         if not lo <= hi:                       # no pairs (N <= 1): numpy's range of an empty input
             lo, hi = 0.0, 1.0
         if lo == hi:                           # numpy: a single value gets a bin of width 1 around it
             lo, hi = lo - 0.5, hi + 0.5
     edges = make_edges(lo, hi)
-    raw, stats = _hist_scan(x, y32, edges, bins)
+    raw, stats = _hist_scan(x, y32, edges, bins, code)
     counts = raw[:, 1:bins + 1].clone()
     outside = torch.stack([raw[:, 0], raw[:, bins + 1]], dim=1)
     if clamp:
@@ -390,16 +390,16 @@ def edge_index_to_sparse_csc_tensor(x, edge_index):
 # kNN similarity graph: the edges the aggregation layers consume, straight from x
 # ---------------------------------------------------------------------------
 def knn_graph(x: torch.Tensor, k: int, exclude_self: bool = True):
-    """For every node the ``k`` most cosine-similar nodes (``sngnn_knn_graph``: tiled fp32
-    MFMA with a fused per-row top-k; the [N, N] similarity of dense.py:138-141 is never
-    stored).  Returns (idx int64 [N, k] in rank order, -1 padded; sim fp32 [N, k])."""
-    x = _x(x)
+    """For every node the ``k`` most cosine-similar nodes (``sngnn_knn_graph``: tiled fp32 MFMA with a fused per-row
+    top-k; the [N, N] similarity of dense.py:138-141 is never stored; an fp16 / bf16 table that takes the fused scan is
+    read as stored, ``_scan_tables``: the same lists).  Returns (idx int64 [N, k] in rank order, -1 padded; sim fp32 [N, k])."""
+    (x,), code = _scan_tables(x, square=True)
     n, f = x.shape
     lib = _lib.load()
     idx = torch.empty((n, k), dtype=torch.int32, device=x.device)
     sim = torch.empty((n, k), dtype=torch.float32, device=x.device)
     ws = _lib.workspace("knn", lib.sngnn_knn_workspace_bytes(n, int(k)), x.device)
-    _lib.call("sngnn_knn_graph", x.device, x, n, f, int(k), int(bool(exclude_self)), idx, sim, ws)
+    _call_knn_graph(code, x, n, f, int(k), int(bool(exclude_self)), idx, sim, ws)
     return idx.long(), sim
 
 

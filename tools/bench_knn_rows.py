@@ -49,7 +49,7 @@ def interleaved(arms):
 
 
 def splits(m, n, f):
-    """The column splits ``sngnn_knn_query`` uses (csrc/knn.hip, knn_query_plan) for aligned tables at knob 5 / 6 = 0."""
+    """The column splits ``sngnn_knn_query`` uses (csrc/knn_scan.h, knn_query_plan) for aligned tables at knob 5 / 6 = 0."""
     wide = f in (32, 64, 96, 128)
     rows_wg, cols_tile = (256, 64) if wide else (128, 128)
     nrb, nct = -(-m // rows_wg), -(-n // cols_tile)
