@@ -1393,6 +1393,38 @@ int64_t sngnn_knn_query_workspace_bytes(int64_t M, int64_t N, int k);
 int sngnn_knn_query(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, int k, int64_t self_offset,
                     int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
 /*
+ * The threshold (epsilon-neighbourhood) graph of the same two tables: for every query row i EVERY eligible base row j
+ * with cosine s_ij >= thr, as CSR - a row has as many entries as the cut gives it, none or thousands, where the kNN
+ * lists stop at 32.  No M x N matrix: the scan of sngnn_knn_query runs twice, a count pass and a fill pass around the
+ * caller's exclusive scan (csrc/cosine_thresh_scan.h).
+ *   Entry rule: (i, j) is an entry iff base row j is eligible for query i - sngnn_knn_query's rule: self_offset = r >= 0
+ *   excludes base row r + i, -1 excludes nothing - and s_ij >= thr in fp32 (a cosine of exactly thr IS an entry; a NaN
+ *   value is none; thr = -inf keeps every eligible pair).  s_ij is the value sngnn_knn_query forms for the same tables
+ *   and knob state - acc * (inv_i * inv_j) + 0.0f on the same engine variant (F, knobs 5 and 6, the 16-byte alignment
+ *   of both tables) - so a stored value is never -0.0 and a row range has the square call's rows bit for bit.
+ *   Non-finite table entries are outside the contract.
+ * sngnn_cosine_threshold_count   count dev i32 [M]: the exact number of entries of every row (overwritten; the caller
+ *                                zeroes nothing).
+ * sngnn_cosine_threshold_fill    rowptr dev i64 [M + 1]: the caller's exclusive scan of count, nnz its total.  Row i's
+ *                                entries go to [rowptr[i], rowptr[i + 1]) of out_col dev i32 [nnz] / out_val dev f32
+ *                                [nnz], column ids ASCENDING.  nnz > 2^31 - 1: SNGNN_ERANGE.
+ *                                The fill RELIES on what the matching count call left in the workspace - both tables'
+ *                                inverse norms and, per column range, the number of a row's entries in the ranges
+ *                                before it: call it with the count's arguments (tables, shapes, thr, self_offset, knob
+ *                                state) and the count's workspace, with nothing else using that workspace in between.
+ * NaN thr, NULL, a bad shape, self_offset + M > N, M or N >= 2^31: SNGNN_EINVAL; a refused call launches nothing.
+ * M == 0 launches nothing; N == 0: every count is 0.  No atomics: the same bits on every run.  Both only enqueue on
+ * `stream` (capturable).
+ *   workspace: sngnn_cosine_threshold_workspace_bytes(M, N) - the inverse norms and 4 bytes per row and column range
+ *   (up to 320 ranges when there are few query rows)
+ */
+int64_t sngnn_cosine_threshold_workspace_bytes(int64_t M, int64_t N);
+int sngnn_cosine_threshold_count(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, float thr,
+                                 int64_t self_offset, int32_t *count, void *workspace, void *stream);
+int sngnn_cosine_threshold_fill(const float *xq, int64_t M, const float *xb, int64_t N, int64_t F, float thr,
+                                int64_t self_offset, const int64_t *rowptr, int64_t nnz, int32_t *out_col,
+                                float *out_val, void *workspace, void *stream);
+/*
  * The cosine scans straight from an fp16 / bf16 table (2 F bytes a row, read as stored - no fp32 copy): the kNN graph,
  * the two-table query and the histogram above on the tile engine's half forms.  A value of such a table has two
  * (fp16) resp. one (bf16) of the three bf16 planes the fp32 scan splits a float into; the planes it has are used as

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from .knn_query import _call_cosine_hist, _call_knn_graph, _scan_tables, knn_edge_index_partitioned, knn_edge_index_rows, knn_graph_partitioned, knn_graph_rows, knn_query  # noqa: F401 (a row range / query set against a base)
 from .sparse_cosine import cosine_similarity_sparse_csr, knn_edge_index_sparse, knn_graph_sparse, node_similarity_sparse_histogram, sparse_columns  # noqa: F401 (sparse S at any N)
+from .threshold_graph import cosine_similarity_threshold_csr, threshold_degrees, threshold_edge_index, threshold_edge_index_rows, threshold_graph_rows, threshold_query  # noqa: F401 (every pair above a cut, as CSR)
 
 
 def _x(x: torch.Tensor) -> torch.Tensor:
