@@ -1453,6 +1453,26 @@ int sngnn_knn_query_half(const void *xq, int64_t M, const void *xb, int dtype, i
                          int64_t self_offset, int32_t *nbr_idx, float *nbr_sim, void *workspace, void *stream);
 int sngnn_cosine_hist_half(const void *x, int dtype, int64_t N, int64_t F, const int32_t *y, const float *edges,
                            int bins, unsigned long long *counts, double *stats, void *workspace, void *stream);
+/*
+ * The threshold graph straight from two fp16 / bf16 tables: sngnn_cosine_threshold_count / _fill on the same half
+ * forms (csrc/cosine_thresh_half.hip).  BOTH passes read the tables as stored and issue 4 (fp16) resp. 1 (bf16) of the
+ * 8 matrix instructions per product; inverse norms (the fp32 chain on the widened values), entry rule, value
+ * expression, column ranges and the range prefix are the fp32 pair's.  On tables of finite values count, out_col and
+ * out_val are those of the fp32 pair on the widened tables, bit for bit; a non-finite entry is outside that statement.
+ *   dtype   SNGNN_DTYPE_F16 or SNGNN_DTYPE_BF16, the type of BOTH tables
+ * Refused, nothing launched and no output or workspace byte written: everything the fp32 pair refuses (shapes, NaN
+ * thr, self_offset, nnz - SNGNN_ERANGE past 2^31 - 1 -, NULL), a dtype that is neither half type, what
+ * sngnn_cosine_scan_half_supported(F, dtype) refuses, and a table whose base is not 16-byte aligned (SNGNN_EINVAL).
+ * M == 0, N == 0 and nnz == 0 behave as in the fp32 pair.  The count / fill contract is the fp32 pair's: the fill of
+ * THIS pair is called with the arguments and the workspace of the count of THIS pair, nothing in between on that
+ * workspace (the fp32 count's column ranges may differ).  Both only enqueue on `stream` (capturable).
+ *   workspace: sngnn_cosine_threshold_workspace_bytes(M, N) - the fp32 pair's size and layout
+ */
+int sngnn_cosine_threshold_count_half(const void *xq, int64_t M, const void *xb, int dtype, int64_t N, int64_t F,
+                                      float thr, int64_t self_offset, int32_t *count, void *workspace, void *stream);
+int sngnn_cosine_threshold_fill_half(const void *xq, int64_t M, const void *xb, int dtype, int64_t N, int64_t F,
+                                     float thr, int64_t self_offset, const int64_t *rowptr, int64_t nnz,
+                                     int32_t *out_col, float *out_val, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------
  * R replicas of one 1-layer model trained together (sngnn_amd/splits.py): the sweep scripts'

@@ -78,7 +78,7 @@ SIGNATURES = {
     "sngnn_bn_post_backward": (_i32, [_vp, _vp, _i64, _i32] + [_vp] * 5 + [_f32, _vp, _f32] + [_vp] * 5),
     "sngnn_knn_workspace_bytes": (_i64, [_i64, _i32]), "sngnn_knn_query_workspace_bytes": (_i64, [_i64, _i64, _i32]), "sngnn_knn_graph_route": (_i32, [_i64]), "sngnn_cosine_threshold_workspace_bytes": (_i64, [_i64, _i64]),
     "sngnn_knn_graph": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]), "sngnn_knn_query": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]), "sngnn_knn_graph_half": (_i32, [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]), "sngnn_knn_query_half": (_i32, [_vp, _i64, _vp, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "sngnn_cosine_threshold_count": (_i32, [_vp, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp]), "sngnn_cosine_threshold_fill": (_i32, [_vp, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sngnn_cosine_threshold_count": (_i32, [_vp, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp]), "sngnn_cosine_threshold_fill": (_i32, [_vp, _i64, _vp, _i64, _i64, _f32, _i64, _vp, _i64, _vp, _vp, _vp, _vp]), "sngnn_cosine_threshold_count_half": (_i32, [_vp, _i64, _vp, _i32, _i64, _i64, _f32, _i64, _vp, _vp, _vp]), "sngnn_cosine_threshold_fill_half": (_i32, [_vp, _i64, _vp, _i32, _i64, _i64, _f32, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sngnn_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]), "sngnn_scatter_sum_rows": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_weighted_gather_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]), "sngnn_weighted_scatter_sum_rows": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "sngnn_pair_dot_rows": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),

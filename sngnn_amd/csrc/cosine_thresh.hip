@@ -1,32 +1,11 @@
 // Threshold similarity graph on fp32 tables: sngnn_cosine_threshold_count / _fill (the kernels: cosine_thresh_scan.h).
 // Engine variant and column ranges by sngnn_knn_query's rule (knn.hip): F, knobs 5 and 6, the 16-byte alignment of
 // both tables - so every value is the one that entry forms, and the count and the fill of one call agree.
-#include <cmath>
-
 #include "cosine_thresh_scan.h"
 
 using namespace sngnn;
 
 namespace {
-
-// workspace: the inverse norms of the queries and of the base, then the column ranges' counts [ns][M]
-struct ThreshWs { float *invq, *invb; int32_t *part; };
-ThreshWs thresh_ws(void *workspace, int64_t M, int64_t N)
-{
-    char *w = (char *)workspace;
-    return {(float *)w, (float *)(w + (M + 63) / 64 * 256), (int32_t *)(w + (M + 63) / 64 * 256 + (N + 63) / 64 * 256)};
-}
-
-// the refusals the two entries share
-int thresh_check(int64_t M, int64_t N, int64_t F, float thr, int64_t self_offset)
-{
-    SN_REQUIRE(M >= 0 && N >= 0 && F >= 1, SNGNN_EINVAL, "bad shape");
-    SN_REQUIRE(M < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), SNGNN_EINVAL, "too many rows");
-    SN_REQUIRE(!std::isnan(thr), SNGNN_EINVAL, "thr is NaN");
-    SN_REQUIRE(self_offset >= -1 && (self_offset < 0 || self_offset + M <= N), SNGNN_EINVAL,
-               "self_offset: the queries are not rows [self_offset, self_offset + M) of the base");
-    return SNGNN_OK;
-}
 
 // one pass of the scan (FILL: the second).  sngnn_knn_query's dispatch.
 template <bool FILL>

@@ -25,22 +25,28 @@
 //
 // No atomics in either pass; the same bits on every run.  Both passes must take the same engine variant and plan:
 // cosine_thresh.hip derives both from the same arguments and knob state.
+//
+// This header holds the kernels, the workspace layout and the shared refusals; cosine_thresh.hip launches them on fp32
+// tables, cosine_thresh_half.hip on fp16 / bf16 tables (sngnn_cosine_threshold_count_half / _fill_half: the engine's
+// PL < 3, see knn_half.hip).
 #pragma once
 #include <algorithm>
+#include <cmath>
 
 #include "knn_scan.h"          // knn_query_plan (and cosine_tiles.h)
 
 namespace sngnn {
 
-template <int FH, bool BF3, int NWV, int CB, bool FILL>
-__global__ __launch_bounds__(64 * NWV) void k_cosine_thresh(const float *__restrict__ xq, int64_t M, const float *__restrict__ invq,
-                                                           const float *__restrict__ xb, int64_t N, int64_t F,
+template <int FH, bool BF3, int NWV, int CB, bool FILL, int PL = 3>
+__global__ __launch_bounds__(64 * NWV) void k_cosine_thresh(const typename CosineTiles<FH, BF3, NWV, CB, PL>::XT *__restrict__ xq, int64_t M,
+                                                           const float *__restrict__ invq,
+                                                           const typename CosineTiles<FH, BF3, NWV, CB, PL>::XT *__restrict__ xb, int64_t N, int64_t F,
                                                            const float *__restrict__ invb, float thr, int64_t self,
                                                            int tiles_per_split, int32_t *__restrict__ part,
                                                            const int64_t *__restrict__ rowptr, int64_t nnz,
                                                            int32_t *__restrict__ out_col, float *__restrict__ out_val)
 {
-    using Eng = CosineTiles<FH, BF3, NWV, CB>;
+    using Eng = CosineTiles<FH, BF3, NWV, CB, PL>;
     constexpr int KC = Eng::KC, KR = Eng::KR;
     __shared__ float sA[Eng::SA_FLOATS];
     __shared__ __align__(16) float sB[Eng::SB_FLOATS];
@@ -173,6 +179,25 @@ static __global__ __launch_bounds__(256) void k_thresh_zero(int32_t *__restrict_
 static int thresh_ranges_max(int64_t M, int64_t N)
 {
     return std::max(knn_query_plan(M, N, KN_M, KN_M).ns, knn_query_plan(M, N, 256, 64).ns);
+}
+
+// workspace: the inverse norms of the queries and of the base, then the column ranges' counts [ns][M]
+struct ThreshWs { float *invq, *invb; int32_t *part; };
+static inline ThreshWs thresh_ws(void *workspace, int64_t M, int64_t N)
+{
+    char *w = (char *)workspace;
+    return {(float *)w, (float *)(w + (M + 63) / 64 * 256), (int32_t *)(w + (M + 63) / 64 * 256 + (N + 63) / 64 * 256)};
+}
+
+// the refusals every count and fill entry shares
+static inline int thresh_check(int64_t M, int64_t N, int64_t F, float thr, int64_t self_offset)
+{
+    SN_REQUIRE(M >= 0 && N >= 0 && F >= 1, SNGNN_EINVAL, "bad shape");
+    SN_REQUIRE(M < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), SNGNN_EINVAL, "too many rows");
+    SN_REQUIRE(!std::isnan(thr), SNGNN_EINVAL, "thr is NaN");
+    SN_REQUIRE(self_offset >= -1 && (self_offset < 0 || self_offset + M <= N), SNGNN_EINVAL,
+               "self_offset: the queries are not rows [self_offset, self_offset + M) of the base");
+    return SNGNN_OK;
 }
 
 }  // namespace sngnn

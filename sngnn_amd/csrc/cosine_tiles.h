@@ -2,9 +2,10 @@
 // row block against one column tile after another, on the matrix cores at fp32 rounding, never stored.
 // Three consumers: knn_scan.h ranks the values of a tile (k_knn_mfma), cosine_hist_scan.h counts them
 // (k_cosine_hist), cosine_thresh_scan.h keeps the ones that reach a threshold (k_cosine_thresh); knn.hip /
-// cosine_hist.hip / cosine_thresh.hip launch them on fp32 tables, knn_half.hip / cosine_hist_half.hip on
-// fp16 / bf16 tables.  The consumer owns the tile loop, the accumulators and the epilogue; the engine owns
-// the rows' register operands, the panels in flight and the staging + MFMA loops of one tile.
+// cosine_hist.hip / cosine_thresh.hip launch them on fp32 tables, knn_half.hip / cosine_hist_half.hip /
+// cosine_thresh_half.hip on fp16 / bf16 tables.  The consumer owns the tile loop, the accumulators and the
+// epilogue; the engine owns the rows' register operands, the panels in flight and the staging + MFMA loops of
+// one tile.
 // The rows may come from a table of their own (sngnn_knn_query: load_rows takes it, products<true> is told of it).
 //
 // FH > 0 (F == 2 FH, FH a multiple of 16, F <= 128): the wave's 32 rows never change, so their

@@ -19,7 +19,8 @@ KNN_MAX_K = 32          # the widest selection of ``sngnn_knn_query`` (and of ``
 # scan beat the widening route in the measurement (profiles/knn_half.txt).  The results are the same bits either way.
 _HALF_CODES = {torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 KNN_HALF_DEFAULT = (torch.float16, torch.bfloat16)
-KNN_HALF = {"0": (), "1": tuple(_HALF_CODES)}.get(os.environ.get("SNGNN_KNN_HALF", ""), KNN_HALF_DEFAULT)
+KNN_HALF_SWITCH = os.environ.get("SNGNN_KNN_HALF", "")          # (read here only; "1" also overrides threshold_graph's default)
+KNN_HALF = {"0": (), "1": tuple(_HALF_CODES)}.get(KNN_HALF_SWITCH, KNN_HALF_DEFAULT)
 
 
 def _scan_tables(*tables, square=False):

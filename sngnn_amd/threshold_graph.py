@@ -2,7 +2,9 @@
 whose cosine reaches ``thr`` - as many as the cut gives, none for an isolated node, hundreds inside a dense cluster,
 where the kNN lists stop at 32 - as CSR, on the matrix cores, no M x N similarity stored (``sngnn_cosine_threshold_count``
 / ``_fill``, csrc/cosine_thresh.hip: ``knn_query``'s scan run twice around an exclusive scan).  Column ids ascend within
-a row; every value is the cosine ``knn_query`` returns for that pair, bit for bit.  The public names are re-exported by
+a row; every value is the cosine ``knn_query`` returns for that pair, bit for bit.  Two fp16 / bf16 tables are scanned
+as stored, in both passes (``sngnn_cosine_threshold_count_half`` / ``_fill_half``, csrc/cosine_thresh_half.hip): the
+fp32 call's CSR on the widened tables, bit for bit, without the fp32 copies.  The public names are re-exported by
 ``sngnn_amd.toolbox``."""
 from __future__ import annotations
 
@@ -10,8 +12,15 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, knn_query as _kq
 from .knn_query import _rows
+
+# The storage types whose tables the threshold entries read as stored when SNGNN_KNN_HALF is unset: the ones whose
+# native count + fill beat the widening route in all three rounds of the measurement (profiles/threshold_half.txt).
+# SNGNN_KNN_HALF=0 turns the native scans off, =1 turns both types on - the one switch of the cosine scans, decoded in
+# ``knn_query`` (``KNN_HALF_SWITCH``, ``KNN_HALF``) and read from there at every call; the results are the same bits
+# either way.
+THRESHOLD_HALF_DEFAULT = (torch.float16, torch.bfloat16)
 
 
 def _thr(thr) -> float:
@@ -21,9 +30,17 @@ def _thr(thr) -> float:
     return thr
 
 
+def _scan_tables(*tables):
+    """``knn_query._scan_tables`` under the threshold entries' default: (the fp16 / bf16 tables as stored, their
+    SNGNN_DTYPE_* code) when the native pair takes them, otherwise (contiguous fp32 tables, 0)."""
+    if _kq.KNN_HALF_SWITCH != "1" and tables[0].dtype not in THRESHOLD_HALF_DEFAULT:      # (then intersected with KNN_HALF)
+        from .toolbox import _x
+        return tuple(_x(t) for t in tables), 0
+    return _kq._scan_tables(*tables)
+
+
 def _tables(xq, xb, self_offset):
-    from .toolbox import _x
-    xq, xb = _x(xq), _x(xb)
+    (xq, xb), code = _scan_tables(xq, xb)
     if xq.device != xb.device:
         raise ValueError(f"the queries live on {xq.device}, the base on {xb.device}")
     (m, f), n = xq.shape, xb.size(0)
@@ -32,16 +49,20 @@ def _tables(xq, xb, self_offset):
     off = -1 if self_offset is None else int(self_offset)
     if off < -1 or (off >= 0 and off + m > n):
         raise ValueError(f"self_offset {self_offset}: the {m} queries are not rows [{off}, {off + m}) of a base of {n}")
-    return xq, xb, m, n, f, off
+    return xq, xb, m, n, f, off, code
 
 
-def _count(xq, xb, m, n, f, thr, off):
-    """The count pass: (count int32 [M], the workspace the matching fill must be given)."""
+def _count(xq, xb, m, n, f, thr, off, code):
+    """The count pass - on the tables as stored when ``code`` names their half type: (count int32 [M], the workspace
+    the matching fill, of the same entry pair, must be given)."""
     count = torch.empty(m, dtype=torch.int32, device=xq.device)
     ws = None
     if m:
         ws = _lib.workspace("cosine_threshold", _lib.load().sngnn_cosine_threshold_workspace_bytes(m, n), xq.device)
-        _lib.call("sngnn_cosine_threshold_count", xq.device, xq, m, xb, n, f, thr, off, count, ws)
+        if code:
+            _lib.call("sngnn_cosine_threshold_count_half", xq.device, xq, m, xb, code, n, f, thr, off, count, ws)
+        else:
+            _lib.call("sngnn_cosine_threshold_count", xq.device, xq, m, xb, n, f, thr, off, count, ws)
     return count, ws
 
 
@@ -50,8 +71,8 @@ def threshold_degrees(xq: torch.Tensor, xb: torch.Tensor, thr: float, self_offse
     int64 [M], the row lengths of ``threshold_query`` - the count pass alone.  ``self_offset`` as in ``knn_query``.
     Only enqueues: it can be captured in a graph."""
     thr = _thr(thr)
-    xq, xb, m, n, f, off = _tables(xq, xb, self_offset)
-    return _count(xq, xb, m, n, f, thr, off)[0].long()
+    xq, xb, m, n, f, off, code = _tables(xq, xb, self_offset)
+    return _count(xq, xb, m, n, f, thr, off, code)[0].long()
 
 
 def threshold_query(xq: torch.Tensor, xb: torch.Tensor, thr: float, self_offset=None) -> torch.Tensor:
@@ -60,14 +81,16 @@ def threshold_query(xq: torch.Tensor, xb: torch.Tensor, thr: float, self_offset=
     [M, N] with int32 indices and fp32 values - ``cosine_similarity_sparse_csr``'s convention - column ids ascending
     within a row, the values those of ``knn_query`` bit for bit (never -0.0), the same bits on every run.
     ``self_offset = r``: the queries are rows [r, r + M) of the base and (i, r + i) is no entry; ``None``: every pair is
-    eligible.  fp32 work on GPU tensors (others are cast; an fp16 / bf16 table is widened).  Count, scan, ONE host read
-    (nnz), fill: it cannot be captured in a graph."""
+    eligible.  fp32 work on GPU tensors (others are cast).  Two fp16 / bf16 tables of one type are scanned as stored
+    when that type is enabled (``THRESHOLD_HALF_DEFAULT``, ``SNGNN_KNN_HALF``; ``knn_query._scan_tables`` has the
+    other conditions) - the fp32 call's result on the widened tables, bit for bit; otherwise they are widened.  Count,
+    scan, ONE host read (nnz), fill: it cannot be captured in a graph."""
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("threshold_query reads nnz on the host between its count and its fill and "
                            "cannot be captured in a graph")
     thr = _thr(thr)
-    xq, xb, m, n, f, off = _tables(xq, xb, self_offset)
-    count, ws = _count(xq, xb, m, n, f, thr, off)
+    xq, xb, m, n, f, off, code = _tables(xq, xb, self_offset)
+    count, ws = _count(xq, xb, m, n, f, thr, off, code)
     crow = torch.zeros(m + 1, dtype=torch.int64, device=xq.device)
     crow[1:] = torch.cumsum(count, 0)
     nnz = int(crow[-1])
@@ -78,7 +101,10 @@ def threshold_query(xq: torch.Tensor, xb: torch.Tensor, thr: float, self_offset=
     val = torch.empty(nnz, dtype=torch.float32, device=xq.device)
     if m:
         # (the fill reads what the count left in ws: same arguments, nothing in between on this stream)
-        _lib.call("sngnn_cosine_threshold_fill", xq.device, xq, m, xb, n, f, thr, off, crow, nnz, col, val, ws)
+        if code:
+            _lib.call("sngnn_cosine_threshold_fill_half", xq.device, xq, m, xb, code, n, f, thr, off, crow, nnz, col, val, ws)
+        else:
+            _lib.call("sngnn_cosine_threshold_fill", xq.device, xq, m, xb, n, f, thr, off, crow, nnz, col, val, ws)
     return torch.sparse_csr_tensor(crow.to(torch.int32), col, val, size=(m, n))
 
 
@@ -91,9 +117,9 @@ def cosine_similarity_threshold_csr(x: torch.Tensor, thr: float, exclude_self: b
 
 def threshold_graph_rows(x: torch.Tensor, rows, thr: float, exclude_self: bool = True) -> torch.Tensor:
     """Rows [r0, r1) of ``cosine_similarity_threshold_csr(x, thr)`` - bit for bit - as a CSR [r1 - r0, N] with GLOBAL
-    column ids: what the rank that owns that node range needs.  The slice is a view; nothing is copied."""
-    from .toolbox import _x
-    x = _x(x)
+    column ids: what the rank that owns that node range needs.  The slice is a view; nothing is copied (a row slice of
+    a contiguous fp16 / bf16 table of a supported width stays 16-byte aligned, so it is scanned as stored too)."""
+    (x,), _ = _scan_tables(x)
     r0, r1 = _rows(x, rows)
     return threshold_query(x[r0:r1], x, thr, r0 if exclude_self else None)
 

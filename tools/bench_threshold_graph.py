@@ -13,7 +13,13 @@ runs of each arm, INTERLEAVED in one process; the input is prepared once; one JS
     c  knn_query(x, x, 16, 0): the yardstick, one scan with its selection
     d  at three thresholds (about 1, 16 and 256 entries a row, read off node_similarity_histogram of the table):
        count alone, count + fill; nnz and the peak of allocated device memory of a count + fill
-    e  rows [0, N / 8) through threshold_graph_rows at the middle threshold"""
+    e  rows [0, N / 8) through threshold_graph_rows at the middle threshold
+
+``--half`` (profiles/threshold_half.txt): the same 169 343 x 128 rows rounded to bf16 / fp16, at the cut that gives
+about 16 entries a row.  Per type, interleaved: (a) the route before - ``knn_query.KNN_HALF = ()`` around the call, so
+both fp32 casts are inside the timed region - against (b) the native ``_half`` pair, for the count alone, count + fill
+and range 0 of 8; the fp32 scan on a table widened beforehand as the yardstick; the peak of a count + fill for (a) and
+(b).  (a) and (b) are asserted to return equal crow / col and values of equal bits before anything is timed."""
 import json
 import os
 import sys
@@ -132,6 +138,64 @@ def config4():
     print(json.dumps(line), flush=True)
 
 
+def half():
+    from sngnn_amd import knn_query as KQ, threshold_graph as TG
+    TG.THRESHOLD_HALF_DEFAULT = tuple(KQ._HALF_CODES)          # (b) is native whatever the shipped default is
+    both = KQ.KNN_HALF
+    assert set(both) == set(KQ._HALF_CODES), "SNGNN_KNN_HALF=0 leaves no native arm to time"
+
+    def widened(fn):
+        def run():
+            KQ.KNN_HALF = ()
+            try:
+                return fn()
+            finally:
+                KQ.KNN_HALF = both
+        return run
+
+    n, f = 169343, 128
+    x32 = torch.randn(n, f, device=dev)
+    bounds = Partition.even_bounds(n, 8)
+    for dtype, tag in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
+        xh = x32.to(dtype)
+        xw = xh.float()                                        # the yardstick's table: widened beforehand
+        thr, above = cut_for(xw, 16)
+        rows = (bounds[0], bounds[1])
+        native = {"count": lambda: T.threshold_degrees(xh, xh, thr, 0),
+                  "count_fill": lambda: T.cosine_similarity_threshold_csr(xh, thr),
+                  "range0_of_8": lambda: T.threshold_graph_rows(xh, rows, thr)}
+        # equal results before anything is timed
+        for name in ("count_fill", "range0_of_8"):
+            a, b = widened(native[name])(), native[name]()
+            assert torch.equal(a.crow_indices(), b.crow_indices()) and torch.equal(a.col_indices(), b.col_indices()), (tag, name)
+            assert torch.equal(a.values().view(torch.int32), b.values().view(torch.int32)), (tag, name)
+            if name == "count_fill":
+                nnz = int(b.values().numel())
+                assert torch.equal(native["count"](), b.crow_indices().long().diff()), tag
+                assert torch.equal(widened(native["count"])(), b.crow_indices().long().diff()), tag
+            del a, b
+        arms = {}
+        for name, fn in native.items():
+            arms[f"a_widen_{name}_ms"] = widened(fn)
+            arms[f"b_native_{name}_ms"] = fn
+        arms["fp32_count_ms"] = lambda: T.threshold_degrees(xw, xw, thr, 0)
+        arms["fp32_count_fill_ms"] = lambda: T.cosine_similarity_threshold_csr(xw, thr)
+        res = interleaved(arms)
+        line = {"tool": "bench_threshold_graph", "case": "half", "dtype": tag, "N": n, "F": f, "runs": RUNS, "thr": thr,
+                "pairs_above_by_histogram": above, "nnz": nnz, "entries_per_row": round(nnz / n, 2), "results_equal": True,
+                "rows_of_range0": list(rows),
+                "a_widen_count_fill_peak_MiB": peak_mb(widened(native["count_fill"])),
+                "b_native_count_fill_peak_MiB": peak_mb(native["count_fill"]),
+                "native_won_every_round_of_count_fill": all(b < a for a, b in zip(res["a_widen_count_fill_ms"],
+                                                                                  res["b_native_count_fill_ms"]))}
+        line.update(res)
+        print(json.dumps(line), flush=True)
+        del xh, xw
+
+
 if __name__ == "__main__":
-    small()
-    config4()
+    if "--half" in sys.argv[1:]:
+        half()
+    else:
+        small()
+        config4()
